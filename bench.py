@@ -2,6 +2,7 @@
 """Headline benchmark: landmark vectors per second of the fill + site-assignment pass.
 
     python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5|C2h|C2t] [--frames F] [--algo dotprod|mcl]
+                    [--dump-outputs DIR] [--full]
 
 Workload: BASELINE.json configs[1], "C2": synthetic 64-mobile / 512-landmark orthorhombic cell (SCgrid(8,8,8), 32.0 x
 35.2 x 38.4 A, A = 576 atoms), 100 000 frames PER GPU at every N (weak scaling: rank r holds frames [r*F, (r+1)*F) of
@@ -12,12 +13,20 @@ C5: the ragged FCC host, 62 500 frames per GPU, end-to-end run with the mcl plug
 C2 shape on a hexagonal / triclinic cell).  One "step" = one pass of the hot path over the resident trajectory: wrap +
 static-lattice check + landmark vector of every (frame, mobile ion) + cosine assignment to the fitted site centres ->
 int64 label + float64 confidence per (frame, ion).  Frames are resident in HBM before the timed region; the site
-centres come from the product's own end-to-end `run()` on the same trajectory (outside the timed region; it is run
-three times - `cold_seconds` is the first run of the process, `end_to_end_run.seconds` the faster of the two warm runs
-behind it incl. jump detection, both listed in `warm_runs_seconds`).
-At N = 1 the default line also carries the other BASELINE configurations a GPU can hold (`configs`: C3, one GPU's share
-of C4 and of C5), each timed by a child process running `bench.py --config <it>` - a fresh process, because tens of GB of
-device buffers of another size class in the same process cost their hipFree / hipMalloc in whoever runs next.
+centres come from the product's own end-to-end `run()` on the same trajectory (outside the timed region).
+
+A plain run sets up (trajectory, one `run()` for the site centres, the resident context), warms up, times the K steps,
+writes the outputs if asked to and prints the line.  `--dump-outputs DIR`: what the last timed step computed, as
+`HipContext.assignments()` hands it out (`labels.npy`, `confidences.npy` per frame and mobile ion, `site_counts.npy`),
+float64, with `frame_index.npy` naming the frames kept (a fixed, seeded sample when all of them would exceed 48 MiB;
+at N > 1 rank 0's frames); the inputs are seeded, so two builds run with the same arguments can be compared output for
+output.
+`--full` adds everything beside the headline: the end-to-end `run()` record (run three times - `cold_seconds` is the
+first run of the process, `end_to_end_run.seconds` the faster of the two warm runs behind it incl. jump detection, both
+listed in `warm_runs_seconds`), further timed regions (`ms_per_step_regions`), the label checks, the CPU baseline and,
+at N = 1, the other BASELINE configurations a GPU can hold (`configs`: C3, one GPU's share of C4 and of C5), each timed
+by a child process running `bench.py --full --config <it>` - a fresh process, because tens of GB of device buffers of
+another size class in the same process cost their hipFree / hipMalloc in whoever runs next.
 
 N > 1: one process per GPU.  Under `python -m torch.distributed.run ... bench.py --gpus N` the ranks come from
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*; a bare `python bench.py --gpus N` starts the N ranks itself (fresh child
@@ -31,8 +40,8 @@ id, the ranks' agreement that every one of them got its communicator) is a TCP c
 Prints ONE JSON line (rank 0).  `roofline` prices the dominant kernel (k_fill3 unless the tables force the general
 fallback) with the algorithmic bytes of SURVEY.md section 8(d): B = 24*A/M + 16 bytes per landmark vector;
 `roofline.frac_step` is the same for the whole step (ms_per_step: fill + assignment + launch gaps); `roofline.limiter`
-/ `roofline.valu` say what the counters say keeps the kernel below that roofline.  `cpu_baseline` = the oracle's C port of the
-same pass on a bounded cut, one thread (the reference's execution model) and all host cores.
+/ `roofline.valu` say what the counters say keeps the kernel below that roofline.  `cpu_baseline` (`--full`) = the oracle's C
+port of the same pass on a bounded cut, one thread (the reference's execution model) and all host cores.
 """
 import argparse
 import hashlib
@@ -57,10 +66,16 @@ def parse():
     ap.add_argument("--frames", type=int, default=None, help="frames per GPU (default: the configuration's own, below)")
     ap.add_argument("--config", default=None, help="C2 (BASELINE.json configs[1]) at every N; C4 = configs[3]'s per-GPU share")
     ap.add_argument("--algo", default=None, help="clustering plugin of the end-to-end run: dotprod, or mcl (the default of C5)")
-    ap.add_argument("--cpu-frames", type=int, default=1000, help="frames per core of the CPU-baseline cut (0 = skip)")
-    ap.add_argument("--no-scale-ref", action="store_true", help="default workload: skip the extra passes over the other BASELINE configurations (C3, C4's per-GPU share, C5)")
-    ap.add_argument("--repeats", type=int, default=4, help="further timed regions of K steps behind the reported one (min / median of ms_per_step)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float64, 48 MiB at most)")
+    ap.add_argument("--full", action="store_true", help="also the records beside the headline: end-to-end run() (cold and warm), "
+                    "further timed regions, label checks, CPU baseline, the other BASELINE configurations")
+    ap.add_argument("--cpu-frames", type=int, default=1000, help="with --full: frames per core of the CPU-baseline cut (0 = skip)")
+    ap.add_argument("--no-scale-ref", action="store_true", help="with --full, default workload: skip the extra passes over the other BASELINE configurations (C3, C4's per-GPU share, C5)")
+    ap.add_argument("--repeats", type=int, default=4, help="with --full: further timed regions of K steps behind the reported one (min / median of ms_per_step)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # frames per GPU: BASELINE.json's trajectory lengths, the 8-GPU configurations cut into their per-GPU share
@@ -162,65 +177,69 @@ def main():
 
     # --- end-to-end: the product's own LandmarkAnalysis.run() on the whole (N*F-frame) trajectory, this rank's
     #     shard resident on its GPU (upload, tables, fill, exact fit_centers, two predict passes, site centres,
-    #     occupancy check; with N > 1 every exchange step of the path runs on RCCL).  It is reported beside the
-    #     headline and supplies the fitted site centres for the timed pass. ---
-    # The first run of a process also pays for the HIP runtime, the code objects and the first allocations
-    # (`cold_seconds`); the second is what a long-lived analysis process sees per trajectory.
-    t0 = time.time()
-    LandmarkAnalysis(verbose=False, device=local, comm=comm, **la_kw).run(sn, frames)
-    t_cold = time.time() - t0
-    if comm is not None:
-        comm.barrier()
-    # two warm runs, the faster one reported and both listed: the SECOND run of a process comes out 5-8 ms slower than
-    # the third and later ones on some boxes (its uploads are slower; scratch/e2e_walls.py shows the series)
-    warm = []
-    la = st_full = None
-    for _ in range(2):
-        del la, st_full
+    #     occupancy check; with N > 1 every exchange step of the path runs on RCCL).  It supplies the fitted site
+    #     centres for the timed pass; with --full it is also reported beside the headline. ---
+    if not args.full:
+        la = LandmarkAnalysis(verbose=False, device=local, comm=comm, **la_kw)
+        la.run(sn, frames)
+    else:
+        # The first run of a process also pays for the HIP runtime, the code objects and the first allocations
+        # (`cold_seconds`); the second is what a long-lived analysis process sees per trajectory.
+        t0 = time.time()
+        LandmarkAnalysis(verbose=False, device=local, comm=comm, **la_kw).run(sn, frames)
+        t_cold = time.time() - t0
         if comm is not None:
             comm.barrier()
-        t0 = time.time()
-        la = LandmarkAnalysis(verbose=False, device=local, comm=comm, **la_kw)
-        st_full = la.run(sn, frames)
-        t_run_i = time.time() - t0
-        n_jumps = sum(1 for _ in st_full.jumps())      # jump detection (SiteTrajectory.py:307-373): configs[4]'s last step
-        warm.append((time.time() - t0, t_run_i, dict(la.wall_timings)))
-    if comm is not None:                                # every rank reports the same run: the one rank 0 found faster
-        pick = int(comm.bcast(np.array([0 if warm[0][0] <= warm[1][0] else 1], dtype=np.int64))[0])
-    else:
-        pick = 0 if warm[0][0] <= warm[1][0] else 1
-    t_e2e, t_run, walls = warm[pick]
-    e2e = {"frames": F * world, "seconds": round(t_e2e, 4), "cold_seconds": round(t_cold, 4), "warm_runs_seconds": [round(w[0], 4) for w in warm],
-           "algo": args.algo, "run_seconds": round(t_run, 4), "jump_detection_seconds": round(t_e2e - t_run, 4),
-           "jumps": n_jumps, "lvec_per_s": round(world * F * M / t_e2e, 1),
-           "wall_s": {k: round(v, 4) for k, v in walls.items()},
-           "sites": int(st_full.site_network.n_sites), "unassigned_frac": float(st_full.percent_unassigned),
-           "fit": {k: v for k, v in la._ctx.info().items() if k.startswith("fit_")},
-           "exchange": exchange}
-    e2e_labels = st_full.traj.reshape(-1)
-    if world > 1 and args.algo == "dotprod":
-        # how the ranks spent the fit of the exact (relayed) run, and the same run with fit_mode="shard-merge" (every rank
-        # fits its shard, all-gather of the clusters' sufficient statistics, identical merge everywhere): seconds, and
-        # the positions whose site differs from the exact run's once the numberings are matched
-        ft = la.fit_timings or {}
-        e2e["fit_per_rank"] = {k: [round(float(v), 4) for v in comm.allgather(np.array([ft.get(k, 0.0)]))[:, 0]]
-                               for k in ("fit_s", "exchange_s", "merge_s")}
-        comm.barrier()
-        t0 = time.time()
-        la_m = LandmarkAnalysis(verbose=False, device=local, comm=comm, fit_mode="shard-merge", **la_kw)
-        st_m = la_m.run(sn, frames)
-        t_m = time.time() - t0
-        fm = la_m.fit_timings or {}
-        k_exact, k_merge = int(st_full.site_network.n_sites), int(st_m.site_network.n_sites)
-        e2e["shard_merge"] = {
-            "run_seconds": round(t_m, 4), "sites": k_merge,
-            "lvec_per_s": round(world * F * M / t_m, 1),
-            "positions_differing_from_exact": sharding.partition_mismatch_sharded(comm, st_full.traj, st_m.traj, k_exact, k_merge),
-            "positions": int(world * F * M),
-            "clusters_per_rank": fm.get("clusters_per_rank"),
-            "fit_per_rank": {k: [round(float(v), 4) for v in comm.allgather(np.array([fm.get(k, 0.0)]))[:, 0]]
-                             for k in ("fit_s", "exchange_s", "merge_s")}}
-        del la_m, st_m
+        # two warm runs, the faster one reported and both listed: the SECOND run of a process comes out 5-8 ms slower than
+        # the third and later ones on some boxes (its uploads are slower; scratch/e2e_walls.py shows the series)
+        warm = []
+        la = st_full = None
+        for _ in range(2):
+            del la, st_full
+            if comm is not None:
+                comm.barrier()
+            t0 = time.time()
+            la = LandmarkAnalysis(verbose=False, device=local, comm=comm, **la_kw)
+            st_full = la.run(sn, frames)
+            t_run_i = time.time() - t0
+            n_jumps = sum(1 for _ in st_full.jumps())      # jump detection (SiteTrajectory.py:307-373): configs[4]'s last step
+            warm.append((time.time() - t0, t_run_i, dict(la.wall_timings)))
+        if comm is not None:                                # every rank reports the same run: the one rank 0 found faster
+            pick = int(comm.bcast(np.array([0 if warm[0][0] <= warm[1][0] else 1], dtype=np.int64))[0])
+        else:
+            pick = 0 if warm[0][0] <= warm[1][0] else 1
+        t_e2e, t_run, walls = warm[pick]
+        e2e = {"frames": F * world, "seconds": round(t_e2e, 4), "cold_seconds": round(t_cold, 4), "warm_runs_seconds": [round(w[0], 4) for w in warm],
+               "algo": args.algo, "run_seconds": round(t_run, 4), "jump_detection_seconds": round(t_e2e - t_run, 4),
+               "jumps": n_jumps, "lvec_per_s": round(world * F * M / t_e2e, 1),
+               "wall_s": {k: round(v, 4) for k, v in walls.items()},
+               "sites": int(st_full.site_network.n_sites), "unassigned_frac": float(st_full.percent_unassigned),
+               "fit": {k: v for k, v in la._ctx.info().items() if k.startswith("fit_")},
+               "exchange": exchange}
+        e2e_labels = st_full.traj.reshape(-1)
+        if world > 1 and args.algo == "dotprod":
+            # how the ranks spent the fit of the exact (relayed) run, and the same run with fit_mode="shard-merge" (every rank
+            # fits its shard, all-gather of the clusters' sufficient statistics, identical merge everywhere): seconds, and
+            # the positions whose site differs from the exact run's once the numberings are matched
+            ft = la.fit_timings or {}
+            e2e["fit_per_rank"] = {k: [round(float(v), 4) for v in comm.allgather(np.array([ft.get(k, 0.0)]))[:, 0]]
+                                   for k in ("fit_s", "exchange_s", "merge_s")}
+            comm.barrier()
+            t0 = time.time()
+            la_m = LandmarkAnalysis(verbose=False, device=local, comm=comm, fit_mode="shard-merge", **la_kw)
+            st_m = la_m.run(sn, frames)
+            t_m = time.time() - t0
+            fm = la_m.fit_timings or {}
+            k_exact, k_merge = int(st_full.site_network.n_sites), int(st_m.site_network.n_sites)
+            e2e["shard_merge"] = {
+                "run_seconds": round(t_m, 4), "sites": k_merge,
+                "lvec_per_s": round(world * F * M / t_m, 1),
+                "positions_differing_from_exact": sharding.partition_mismatch_sharded(comm, st_full.traj, st_m.traj, k_exact, k_merge),
+                "positions": int(world * F * M),
+                "clusters_per_rank": fm.get("clusters_per_rank"),
+                "fit_per_rank": {k: [round(float(v), 4) for v in comm.allgather(np.array([fm.get(k, 0.0)]))[:, 0]]
+                                 for k in ("fit_s", "exchange_s", "merge_s")}}
+            del la_m, st_m
 
     # --- resident context for the timed pass ---
     ctx = _lib.HipContext(host.cell, device=local)
@@ -290,10 +309,12 @@ def main():
         return float(np.max(comm.allgather(np.array([x]))))
 
     elapsed = max_over_ranks(elapsed)
-    # The reported region is 20 x 0.8 ms: one hiccup is 5 %.  Further regions of K steps each (every one bracketed like
-    # the first; the maximum over the ranks each), for a minimum and a median beside the value.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *ctx.assignments(), F, M)
+    # The reported region is 20 x 0.8 ms: one hiccup is 5 %.  With --full, further regions of K steps each (every one
+    # bracketed like the first; the maximum over the ranks each), for a minimum and a median beside the value.
     regions = [1e3 * elapsed / args.steps]
-    for _ in range(max(0, args.repeats)):
+    for _ in range(max(0, args.repeats) if args.full else 0):
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
@@ -310,15 +331,16 @@ def main():
         rccl_info = {"backend": exchange, "ranks": [int(x) for x in got[:, 0]], "rank": [int(x) for x in got[:, 1]],
                      "device": [int(x) for x in got[:, 2]], "rccl_version": int(got[0, 3])}
         per_rank_value = [float(x) for x in comm.allgather(np.array([F * M * args.steps / elapsed_own]))[:, 0]]
-    labels, confs, counts = ctx.assignments()
-    checks = {"unassigned_frac": float(np.mean(labels < 0)), "sites": int(len(counts)),
-              "labels_equal_end_to_end_run": bool(np.array_equal(labels, e2e_labels)),
-              "label_checksum": int(np.sum(labels[labels >= 0] * 7 + 1) % 1000003)}
+    if args.full:
+        labels, confs, counts = ctx.assignments()
+        checks = {"unassigned_frac": float(np.mean(labels < 0)), "sites": int(len(counts)),
+                  "labels_equal_end_to_end_run": bool(np.array_equal(labels, e2e_labels)),
+                  "label_checksum": int(np.sum(labels[labels >= 0] * 7 + 1) % 1000003)}
 
-    # N > 1, default workload: every rank also times one GPU's share of configs[3] (C4: 125 000 of the 1e6 frames) - the
-    # configuration BASELINE.json names for the 8-GPU run - bracketed by barriers; the record carries the sum over the ranks
+    # N > 1, default workload, --full: every rank also times one GPU's share of configs[3] (C4: 125 000 of the 1e6 frames) -
+    # the configuration BASELINE.json names for the 8-GPU run - bracketed by barriers; the record carries the sum over the ranks
     c4 = None
-    if world > 1 and args.config == "C2" and F == FRAMES_PER_GPU["C2"] and not args.no_scale_ref:
+    if args.full and world > 1 and args.config == "C2" and F == FRAMES_PER_GPU["C2"] and not args.no_scale_ref:
         del frames, la, st_full
         comm.barrier()
         c4 = other_config(args, local, "C4")
@@ -340,8 +362,6 @@ def main():
             "metric": "landmark-vectors/sec (frames x mobile atoms), fill + site assignment",
             "value": value, "unit": "lvec/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "ms_per_step_regions": {"n": len(regions), "min": min(regions), "median": float(np.median(regions)), "max": max(regions),
-                                    "note": "regions of K steps each; the first is the reported one"},
             # how the pass was run: enqueued with defer = 1 (no host synchronisation per pass, every pass's
             # error word collected before the clock stops), labels + confidences written, landmark rows not kept
             "pass_mode": {"workload_id": args.config, "deferred": True, "store_rows": False, "assign": True},
@@ -367,21 +387,24 @@ def main():
             "fill_shape": {k: info.get(k) for k in ("waves_per_workgroup", "frames_per_workgroup", "survivors_per_wave", "task_table_per_wave", "assignment_fused")},
             "stages_ms": {"fill": fill_avg_ms, "predict": float(laps["predict"][0]), "h2d_frames": h2d_ms,
                           "generate_s": round(t_gen, 2)},
-            "end_to_end_run": e2e,
-            "checks": checks,
         }
+        if args.full:
+            out["ms_per_step_regions"] = {"n": len(regions), "min": min(regions), "median": float(np.median(regions)),
+                                          "max": max(regions), "note": "regions of K steps each; the first is the reported one"}
+            out["end_to_end_run"] = e2e
+            out["checks"] = checks
         if comm is not None:
             out["rccl"] = rccl_info
             out["value_per_rank"] = per_rank_value
-        if args.cpu_frames > 0 and world == 1:          # a reported baseline: rank 0 at N=1 only
+        if args.full and args.cpu_frames > 0 and world == 1:          # a reported baseline: rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(host, gen, frames, ref, fit_ctx_centers, M, args.cpu_frames, ncpu)
-        if world == 1 and args.config == "C2" and F == FRAMES_PER_GPU["C2"] and not args.no_scale_ref:
+        if args.full and world == 1 and args.config == "C2" and F == FRAMES_PER_GPU["C2"] and not args.no_scale_ref:
             # The other BASELINE configurations in the same line: C3 (configs[2], the larger one-GPU configuration, at its
             # stated size), one GPU's share of C4 (configs[3]; also `scale_ref`: what `--gpus N --config C4` times on N GPUs)
             # and of C5 (configs[4]: the end-to-end run is Markov clustering + jump detection).
             # Each in a fresh process: tens of GB of device buffers of ANOTHER size class in the same process cost their
             # hipFree / hipMalloc in whoever runs next (C4's warm run() 0.30 s behind C3 in one process, 0.20 s alone), and a
-            # child's record is by construction what `bench.py --config C3` prints on its own (profiles/*_bench_C3.json).
+            # child's record is by construction what `bench.py --full --config C3` prints on its own (profiles/*_bench_C3.json).
             del frames, ctx, la, st_full
             _lib.release_cached_memory()
             out["configs"] = [other_config_child(args, c) for c in ("C3", "C4", "C5")]
@@ -398,10 +421,28 @@ def main():
             comm.close()
 
 
+DUMP_BYTES = 48 << 20       # --dump-outputs: at most this much in all
+DUMP_SEED = 20250611        # the frame sample of --dump-outputs: the same frames in every run with the same arguments
+
+
+def dump_outputs(path, labels, confs, counts, F, M):
+    """What the last timed step computed, as `HipContext.assignments()` hands it to a caller: the site label and the
+    confidence of every (frame, mobile ion) and the number of positions per site, as float64 .npy files (labels and
+    counts are integers well inside float64's exact range).  Every frame while labels + confidences fit DUMP_BYTES, else
+    a fixed, seeded sample of frames in ascending order; `frame_index.npy` names the frames kept either way."""
+    import numpy as np
+    n = min(F, max(1, DUMP_BYTES // (16 * M)))
+    rows = np.arange(F) if n == F else np.sort(np.random.default_rng(DUMP_SEED).choice(F, n, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("labels", labels.reshape(F, M)[rows]), ("confidences", confs.reshape(F, M)[rows]),
+                    ("site_counts", counts), ("frame_index", rows)):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def other_config_child(args, cfg):
-    """`bench.py --config cfg` in a child process (started, not exec'ed: this process keeps its GPU), its line cut down to
+    """`bench.py --full --config cfg` in a child process (started, not exec'ed: this process keeps its GPU), its line cut down to
     the sub-record of `configs`."""
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", str(args.steps), "--warmup", str(args.warmup),
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--config", cfg, "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--cpu-frames", "0", "--repeats", "1", "--no-scale-ref"]
     try:
         p = subprocess.run(cmd, stdout=subprocess.PIPE, env=dict(os.environ), timeout=600)
@@ -411,7 +452,7 @@ def other_config_child(args, cfg):
         d = json.loads(line)
     except Exception as e:      # noqa: BLE001 - the headline line must not depend on a side record
         print("bench.py --config %s failed: %s" % (cfg, e), file=sys.stderr, flush=True)
-        return {"workload": cfg, "error": "%s: %s" % (type(e).__name__, e), "process": "own (`bench.py --config %s`)" % cfg}
+        return {"workload": cfg, "error": "%s: %s" % (type(e).__name__, e), "process": "own (`bench.py --full --config %s`)" % cfg}
     e2e = d["end_to_end_run"]
     return {"workload": d["config"]["workload"] + (" (one GPU's share of the 8-GPU run)" if cfg in ("C4", "C5") else ""),
             "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "steps": d["steps"],
@@ -419,7 +460,7 @@ def other_config_child(args, cfg):
             "roofline": {k: d["roofline"].get(k) for k in ("bound", "kernel", "kernel_ms", "algorithmic_bytes_per_lvec", "peak", "unit", "frac", "frac_step")},
             "fill_shape": d.get("fill_shape"),
             "end_to_end_run": {k: e2e.get(k) for k in ("algo", "seconds", "cold_seconds", "run_seconds", "jumps", "sites", "lvec_per_s", "wall_s")},
-            "process": "own (`bench.py --config %s`)" % cfg}
+            "process": "own (`bench.py --full --config %s`)" % cfg}
 
 
 def other_config(args, device, cfg):

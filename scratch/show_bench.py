@@ -1,4 +1,4 @@
-"""Prints the interesting parts of a bench.py JSON line: scratch/show_bench.py <file>"""
+"""Prints the interesting parts of a `bench.py --full` JSON line: scratch/show_bench.py <file>"""
 import json, sys
 d = json.load(open(sys.argv[1]))
 print({k: d.get(k) for k in ("value", "ms_per_step", "ms_per_step_regions", "pass_mode", "n_gpus")})
