@@ -1,6 +1,6 @@
 #!/bin/bash
-# Counters of the assignment kernels (k_predict_rows_*) over bench.py's C2 step: scratch/pmc_predict.sh [config] ; env passes through
-# (SITATOR_PREDICT_REC=0 for the split-array kernel).  Two or three counters of a block per pass (more make rocprofv3 abort).
+# Counters of the assignment kernels (k_predict_rows_*) over bench.py's C2 step: scratch/pmc_predict.sh [config] ; env passes through.
+# Two or three counters of a block per pass (more make rocprofv3 abort).
 cd /tmp && export TMPDIR=/tmp
 export SITATOR_FILL_AUTOTUNE=0
 R=$GRAFT_REPO_ROOT

@@ -95,25 +95,22 @@ __device__ i64 predict_row_generic(const PredArgs &a, i64 row, int n, double xn)
 }
 
 // One row with at most four entries: a 4-way merge of the (centre-sorted) CSC columns of the row's dimensions.
-// Each step takes the smallest pending centre id and sums its terms in ascending dimension order.  The CSC arrays
-// may live in global memory or (k_predict_rows_lds) in LDS.
-__device__ __forceinline__ i64 predict_row_merge(const PredArgs &a, i64 row, int n, double xn, const i32 *col_ptr,
-                                                  const i32 *col_k, const double *col_val)
+// Each step takes the smallest pending centre id and sums its terms in ascending dimension order.
+__device__ __forceinline__ i64 predict_row_merge(const PredArgs &a, i64 row, int n, double xn)
 {
     i32 d0 = a.row_idx[row], d1 = 0, d2 = 0, d3 = 0;
     double v0 = a.row_val[row], v1 = 0, v2 = 0, v3 = 0;
     if (n > 1) { d1 = a.row_idx[a.N + row]; v1 = a.row_val[a.N + row]; }
     if (n > 2) { d2 = a.row_idx[2 * a.N + row]; v2 = a.row_val[2 * a.N + row]; }
     if (n > 3) { d3 = a.row_idx[3 * a.N + row]; v3 = a.row_val[3 * a.N + row]; }
-    return finish_predict(a, row, merge4_row(n, d0, d1, d2, d3, v0, v1, v2, v3, xn, a.normed != 0, col_ptr, col_k, col_val));
+    return finish_predict(a, row, merge4_row(n, d0, d1, d2, d3, v0, v1, v2, v3, xn, a.normed != 0, a.col_ptr, a.col_k, a.col_val));
 }
 
 // The same merge for rows of up to NW entries (ragged bases: C5 rows hold 5-13).  The column heads live in registers
 // (every index below is a compile-time constant after unrolling); a step costs NW - 1 minimum operations and NW
 // predicated advances, against the row x column x row dense look-ups of predict_row_generic.
 template <int NW>
-__device__ __forceinline__ i64 predict_row_merge_wide(const PredArgs &a, i64 row, int n, double xn, const i32 *col_ptr,
-                                                      const i32 *col_k, const double *col_val)
+__device__ __forceinline__ i64 predict_row_merge_wide(const PredArgs &a, i64 row, int n, double xn)
 {
     ArgMaxQ am;
     am.init();
@@ -125,8 +122,8 @@ __device__ __forceinline__ i64 predict_row_merge_wide(const PredArgs &a, i64 row
         q[s] = 0; e[s] = 0; h[s] = none; v[s] = 0.0;
         if (s < n) {
             const i32 d = a.row_idx[(i64)s * a.N + row];
-            q[s] = col_ptr[d]; e[s] = col_ptr[d + 1]; v[s] = a.row_val[(i64)s * a.N + row];
-            h[s] = q[s] < e[s] ? col_k[q[s]] : none;
+            q[s] = a.col_ptr[d]; e[s] = a.col_ptr[d + 1]; v[s] = a.row_val[(i64)s * a.N + row];
+            h[s] = q[s] < e[s] ? a.col_k[q[s]] : none;
         }
     }
     while (true) {
@@ -139,11 +136,11 @@ __device__ __forceinline__ i64 predict_row_merge_wide(const PredArgs &a, i64 row
 #pragma unroll
         for (int s = 0; s < NW; s++) {
             if (h[s] == cid) {                                       // ascending dimension order (:176)
-                const double t = col_val[q[s]] * v[s];
+                const double t = a.col_val[q[s]] * v[s];
                 dot = first ? t : dot + t;
                 first = false;
                 q[s]++;
-                h[s] = q[s] < e[s] ? col_k[q[s]] : none;
+                h[s] = q[s] < e[s] ? a.col_k[q[s]] : none;
             }
         }
         am.push(dot, cid, xn, a.normed != 0);                       // :177-179
@@ -187,52 +184,16 @@ __global__ __launch_bounds__(PRED_BLOCK) void k_predict_rows(PredArgs a, i32 *wi
         const bool live = row < a.N && predict_row_head(a, row, n, xn);
         const bool wide = live && n > 4;
         list_wide_rows(n, live, row, seg, seg_count, seg_cap, lane);
-        if (live && !wide) predict_row_merge(a, row, n, xn, a.col_ptr, a.col_k, a.col_val);
+        if (live && !wide) predict_row_merge(a, row, n, xn);
     }
 }
 
-// The same with the centres' CSC arrays resident in LDS (they are a few tens of KB: 480 centres of ~8 landmarks at
-// C2).  The merge makes ~35 scattered 4-8 byte reads per row; from global memory each is a 64-address vector load and
-// the kernel is bound by the texture-address path, from LDS they cost a few cycles.  Workgroups are persistent (the
-// arrays are staged once per workgroup) and walk the rows in blocks of their size.
-#define PRED_LDS_BLOCK 512          // threads of a workgroup while several fit a CU; 1024 when the arrays leave room for one or two
-// hist_K > 0: the labels are counted on the way (np.bincount of :92) - per workgroup in LDS, flushed once.
-template <int NTMAX>                 // 512 (registers for six waves per SIMD) or 1024
-__global__ __launch_bounds__(NTMAX) void k_predict_rows_lds(PredArgs a, i32 *wide_list, unsigned *wide_count, i64 seg_cap, int nnzc,
-                                                            int hist_K, u64 *counts)
-{
-    extern __shared__ __attribute__((aligned(16))) char pl_smem[];
-    double *l_val = (double *)pl_smem;
-    i32 *l_ptr = (i32 *)(l_val + nnzc);
-    i32 *l_k = l_ptr + (a.D + 1);
-    unsigned *hist = (unsigned *)(l_k + nnzc);
-    const int NT = NTMAX;                                          // launched with exactly NTMAX threads
-    for (int q = threadIdx.x; q < hist_K; q += NT) hist[q] = 0u;
-    for (int q = threadIdx.x; q < nnzc; q += NT) { l_val[q] = a.col_val[q]; l_k[q] = a.col_k[q]; }
-    for (int q = threadIdx.x; q <= (int)a.D; q += NT) l_ptr[q] = a.col_ptr[q];
-    __syncthreads();
-    i32 *seg = wide_list + (i64)blockIdx.x * seg_cap;
-    unsigned *seg_count = wide_count + 2 * blockIdx.x;
-    const int lane = threadIdx.x & 63;
-    for (i64 r0 = (i64)blockIdx.x * NT; r0 < a.N; r0 += (i64)gridDim.x * NT) {
-        const i64 row = r0 + threadIdx.x;
-        int n = 0;
-        double xn = 0.0;
-        const bool live = row < a.N && predict_row_head(a, row, n, xn);
-        const bool wide = live && n > 4;
-        list_wide_rows(n, live, row, seg, seg_count, seg_cap, lane);
-        if (live && !wide) {
-            const i64 to = predict_row_merge(a, row, n, xn, l_ptr, l_k, l_val);
-            if (hist_K > 0 && to >= 0) atomicAdd(&hist[to], 1u);
-        }
-    }
-    if (hist_K > 0) {
-        __syncthreads();
-        for (int q = threadIdx.x; q < hist_K; q += NT) { const unsigned v = hist[q]; if (v) atomicAdd(&counts[q], (u64)v); }
-    }
-}
-
-// Round 5: the same kernel over PACKED columns.  k_predict_rows_lds' merge is bound by its instructions (62 vector
+// The same with the centres resident in LDS (a few tens of KB: 480 centres of ~8 landmarks at C2).  The merge makes ~35
+// scattered reads per row; from global memory each is a 64-address vector load and the kernel is bound by the
+// texture-address path, from LDS they cost a few cycles.  Workgroups are persistent (the centres are staged once per
+// workgroup) and walk the rows in blocks of their size; hist_K > 0: the labels are counted on the way (np.bincount of
+// :92) - per workgroup in LDS, flushed once.
+// The columns are PACKED.  Over the split CSC arrays in LDS the merge is bound by its instructions (62 vector
 // instructions and four dependent LDS waits per step: an entry's value and the next entry's centre id are two loads from
 // two arrays, each behind its own address arithmetic and an end-of-column compare).  Here a column is a run of 12-byte
 // records {value, centre id} closed by a sentinel record (id = "none"): a column head - id AND value - sits in
@@ -306,15 +267,17 @@ __device__ __forceinline__ Best merge4_rec(int n, i32 d0, i32 d1, i32 d2, i32 d3
     return am.result(xn, normed);
 }
 
-template <int NTMAX>
-__global__ __launch_bounds__(NTMAX) void k_predict_rows_rec(PredArgs a, const unsigned *recs, int nrec, i32 *wide_list, unsigned *wide_count,
-                                                            i64 seg_cap, int hist_K, u64 *counts)
+// 1024 threads: the kernel holds 62 registers, 32 waves per CU while two workgroups fit (C2, 37 KB: 0.116 ms with
+// 3 x 512 threads, 0.111 with 4 x 512, 0.108 with 2 x 1 024; 0.143 with 16 waves)
+#define PRED_REC_BLOCK 1024
+__global__ __launch_bounds__(PRED_REC_BLOCK) void k_predict_rows_rec(PredArgs a, const unsigned *recs, int nrec, i32 *wide_list, unsigned *wide_count,
+                                                                     i64 seg_cap, int hist_K, u64 *counts)
 {
     extern __shared__ __attribute__((aligned(16))) char pl_smem[];
     unsigned *l_rec = (unsigned *)pl_smem;                         // [nrec][3] = entries + a sentinel per column
     unsigned *l_off = l_rec + 3 * nrec;                            // [D] LDS address of a column's first record
     unsigned *hist = l_off + a.D;
-    const int NT = NTMAX;
+    const int NT = PRED_REC_BLOCK;
     for (int q = threadIdx.x; q < hist_K; q += NT) hist[q] = 0u;
     for (int q = threadIdx.x; q < 3 * nrec; q += NT) l_rec[q] = recs[q];
     for (int q = threadIdx.x; q < (int)a.D; q += NT) l_off[q] = (unsigned)(uintptr_t)(LdsWords)l_rec + (unsigned)PRED_REC * (unsigned)(a.col_ptr[q] + q);
@@ -345,19 +308,18 @@ __global__ __launch_bounds__(NTMAX) void k_predict_rows_rec(PredArgs a, const un
     }
 }
 
-// one wide row, centres from `col_*` (global memory or LDS)
-__device__ __forceinline__ void predict_wide_row(const PredArgs &a, i64 row, const i32 *col_ptr, const i32 *col_k, const double *col_val,
-                                                 u64 *counts)
+// one wide row, centres from global memory
+__device__ __forceinline__ void predict_wide_row(const PredArgs &a, i64 row, u64 *counts)
 {
     int n;
     double xn;
     if (!predict_row_head(a, row, n, xn)) return;
     i64 to;
-    if (n <= 8) to = predict_row_merge_wide<8>(a, row, n, xn, col_ptr, col_k, col_val);
-    else if (n <= 10) to = predict_row_merge_wide<10>(a, row, n, xn, col_ptr, col_k, col_val);
-    else if (n <= 16) to = predict_row_merge_wide<16>(a, row, n, xn, col_ptr, col_k, col_val);
+    if (n <= 8) to = predict_row_merge_wide<8>(a, row, n, xn);
+    else if (n <= 10) to = predict_row_merge_wide<10>(a, row, n, xn);
+    else if (n <= 16) to = predict_row_merge_wide<16>(a, row, n, xn);
     else to = predict_row_generic(a, row, n, xn);
-    if (counts && to >= 0) atomicAdd(&counts[to], 1ull);           // the narrow rows were counted by k_predict_rows_lds
+    if (counts && to >= 0) atomicAdd(&counts[to], 1ull);
 }
 
 // the listed rows: workgroup j takes the segments j, j + gridDim.x, ... of the nseg the listing kernel wrote
@@ -367,39 +329,14 @@ __global__ __launch_bounds__(PRED_BLOCK) void k_predict_rows_wide(PredArgs a, co
     for (int sg = blockIdx.x; sg < nseg; sg += gridDim.x) {
         const i64 na = (i64)wide_count[2 * sg], nb = (i64)wide_count[2 * sg + 1];
         const i32 *seg = wide_list + (i64)sg * seg_cap;
-        for (i64 q = threadIdx.x; q < na; q += PRED_BLOCK) predict_wide_row(a, seg[q], a.col_ptr, a.col_k, a.col_val, counts);
-        for (i64 q = threadIdx.x; q < nb; q += PRED_BLOCK) predict_wide_row(a, seg[seg_cap - 1 - q], a.col_ptr, a.col_k, a.col_val, counts);
+        for (i64 q = threadIdx.x; q < na; q += PRED_BLOCK) predict_wide_row(a, seg[q], counts);
+        for (i64 q = threadIdx.x; q < nb; q += PRED_BLOCK) predict_wide_row(a, seg[seg_cap - 1 - q], counts);
     }
 }
 
-// The wide rows with the CSC arrays in LDS: one persistent workgroup per CU (the wide merge's registers allow three
+// The wide rows with the centres in LDS: one persistent workgroup per CU (the wide merge's registers allow three
 // waves per SIMD anyway, so up to ~150 KB of LDS cost no occupancy).  C5: 645 centres x ~12 landmarks = 93 KB.
 #define PRED_WIDE_LDS_BLOCK 1024
-__global__ __launch_bounds__(PRED_WIDE_LDS_BLOCK) void k_predict_rows_wide_lds(PredArgs a, const i32 *wide_list, const unsigned *wide_count,
-                                                                              i64 seg_cap, int nseg, int nnzc, u64 *counts)
-{
-    extern __shared__ __attribute__((aligned(16))) char pl_smem[];
-    __shared__ unsigned any;
-    double *l_val = (double *)pl_smem;
-    i32 *l_ptr = (i32 *)(l_val + nnzc);
-    i32 *l_k = l_ptr + (a.D + 1);
-    if (threadIdx.x == 0) any = 0u;
-    __syncthreads();
-    for (int sg = blockIdx.x + threadIdx.x * gridDim.x; sg < nseg; sg += gridDim.x * PRED_WIDE_LDS_BLOCK)
-        if (wide_count[2 * sg] | wide_count[2 * sg + 1]) any = 1u;
-    __syncthreads();
-    if (!any) return;                                              // nothing for this workgroup: skip the staging
-    for (int q = threadIdx.x; q < nnzc; q += PRED_WIDE_LDS_BLOCK) { l_val[q] = a.col_val[q]; l_k[q] = a.col_k[q]; }
-    for (int q = threadIdx.x; q <= (int)a.D; q += PRED_WIDE_LDS_BLOCK) l_ptr[q] = a.col_ptr[q];
-    __syncthreads();
-    for (int sg = blockIdx.x; sg < nseg; sg += gridDim.x) {
-        const i64 na = (i64)wide_count[2 * sg], nb = (i64)wide_count[2 * sg + 1];
-        const i32 *seg = wide_list + (i64)sg * seg_cap;
-        for (i64 q = threadIdx.x; q < na; q += PRED_WIDE_LDS_BLOCK) predict_wide_row(a, seg[q], l_ptr, l_k, l_val, counts);
-        for (i64 q = threadIdx.x; q < nb; q += PRED_WIDE_LDS_BLOCK) predict_wide_row(a, seg[seg_cap - 1 - q], l_ptr, l_k, l_val, counts);
-    }
-}
-
 // The wide merges over the packed columns (merge4_rec's form; C5's rows hold 5-13 entries: the assignment is half its step).
 template <int NW>
 __device__ __forceinline__ i64 predict_row_merge_wide_rec(const PredArgs &a, i64 row, int n, double xn, const unsigned *l_off)
@@ -553,56 +490,46 @@ extern "C" int sit_set_centers(sit_ctx *c, const double *centers, i64 K, int nor
 // Launch shape of the assignment pass and its counters in the scratch buffer (the label counts, one length word per
 // segment of the wide-row list).
 struct PredPlan {
-    bool narrow_lds, wide_lds, rec;
+    bool narrow_lds, wide_lds;        // packed columns in LDS, else global memory
+    size_t lds, wide_lds_bytes;
     int nt, per_cu, nseg;
     i64 seg_cap;
-    size_t lds, csc;
     unsigned *wcount;
     i32 *wlist;
 };
 
+// The form of the centres, for the narrow and the wide rows apart: packed columns in LDS where they fit (the narrow
+// kernel's LDS holds the label counts too), else global memory.
+static void predict_form(const sit_ctx *c, PredPlan &p)
+{
+    const char *pl = getenv("SITATOR_PREDICT_LDS");                 // "0": keep the centres in global memory (A/B, tests)
+    const bool lds = !(pl && pl[0] == '0') && c->d_col_rec;
+    p.wide_lds_bytes = (size_t)c->csc_nrec * PRED_REC + (size_t)c->D * 4;   // the records (a sentinel a column), the offsets
+    p.lds = p.wide_lds_bytes + (size_t)c->K * 4;
+    p.narrow_lds = lds && p.lds <= 150 * 1024;
+    p.wide_lds = lds && p.wide_lds_bytes <= 150 * 1024;
+}
+
+int wide_list_carve(sit_ctx *c, int nseg, i64 seg_cap, unsigned **wcount, i32 **wlist)
+{
+    const int rc = ensure_scratch(c, ((i64)nseg * seg_cap + 2 * nseg + 64) * 4);
+    if (rc) return rc;
+    *wcount = (unsigned *)c->d_scratch;
+    *wlist = (i32 *)c->d_scratch + ((2 * nseg + 63) / 64 * 64);
+    return SIT_OK;
+}
+
 static int predict_plan(sit_ctx *c, PredPlan &p)
 {
-    if (c->num_cu <= 0) {
-        int v = 0;
-        c->num_cu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0 ? v : 256;
-    }
-    const int ncu = c->num_cu;
-    p.csc = (size_t)c->csc_nnz * 12 + (size_t)(c->D + 1) * 4 + 16;
-    p.lds = p.csc + (size_t)c->K * 4;
-    const char *pl = getenv("SITATOR_PREDICT_LDS");                 // "0": keep the centres in global memory (A/B, tests)
-    const bool no_lds = pl && pl[0] == '0';
-    // the packed columns where they fit (12 bytes an entry + a sentinel a column); SITATOR_PREDICT_REC=0: the split arrays
-    const size_t rec_lds = (size_t)c->csc_nrec * PRED_REC + (size_t)c->D * 4 + (size_t)c->K * 4;
-    const char *pr = getenv("SITATOR_PREDICT_REC");
-    p.rec = rec_lds <= 150 * 1024 && !no_lds && !(pr && pr[0] == '0') && c->d_col_rec;
-    if (p.rec) p.lds = rec_lds;
-    p.narrow_lds = p.lds <= 150 * 1024 && !no_lds;
-    p.wide_lds = p.csc <= 150 * 1024 && !no_lds;
-    // the listing kernel: persistent workgroups, each with its own segment of the wide-row list
-    // LDS: three or four workgroups of 512 threads per CU; larger centre sets (C3: 1 044 centres, 109 KB) leave room
-    // for two or one, of 1024 threads (from global memory C3's assignment took 2.1 ms per 4.5e7 rows)
-    p.nt = !p.narrow_lds ? PRED_BLOCK : (p.lds <= 52 * 1024 ? PRED_LDS_BLOCK : 1024);
-    p.per_cu = !p.narrow_lds ? 8 : (p.lds <= 36 * 1024 ? 4 : (p.lds <= 52 * 1024 ? 3 : (p.lds <= 78 * 1024 ? 2 : 1)));
-    // the packed kernel holds 62 registers in either size: 32 waves per CU while two workgroups fit (C2, 37 KB: 0.116 ms with
-    // 3 x 512 threads, 0.111 with 4 x 512, 0.108 with 2 x 1 024; 0.143 with 16 waves)
-    if (p.rec && p.narrow_lds) {
-        if (p.lds <= 78 * 1024) { p.nt = 1024; p.per_cu = 2; }
-        else { p.nt = 1024; p.per_cu = 1; }
-    }
-    if (const char *ps = getenv("SITATOR_PREDICT_SHAPE")) {         // "NTxPER_CU" (A/B): 512 or 1024 threads, workgroups per CU
-        int ntv = 0, pcv = 0;
-        if (p.narrow_lds && sscanf(ps, "%dx%d", &ntv, &pcv) == 2 && (ntv == PRED_LDS_BLOCK || ntv == 1024) && pcv >= 1 && pcv <= 4 &&
-            (size_t)pcv * (p.lds + 512) <= 160 * 1024) { p.nt = ntv; p.per_cu = pcv; }
-    }
+    predict_form(c, p);
+    // the listing kernel: persistent workgroups, each with its own segment of the wide-row list; in LDS two workgroups
+    // per CU while they fit, larger centre sets (C3: 1 044 centres, 109 KB) leave room for one
+    p.nt = p.narrow_lds ? PRED_REC_BLOCK : PRED_BLOCK;
+    p.per_cu = !p.narrow_lds ? 8 : (p.lds <= 78 * 1024 ? 2 : 1);
     const i64 blocks = (c->N + p.nt - 1) / p.nt;
-    p.nseg = (int)std::min<i64>(blocks, (i64)ncu * p.per_cu);
+    p.nseg = (int)std::min<i64>(blocks, (i64)cu_count(c) * p.per_cu);
     p.seg_cap = (blocks + p.nseg - 1) / p.nseg * p.nt;             // rows a workgroup can meet
-    int rc = ensure_scratch(c, ((i64)p.nseg * p.seg_cap + 2 * p.nseg + 64) * 4);
-    if (rc) return rc;
-    p.wcount = (unsigned *)c->d_scratch;
-    p.wlist = (i32 *)c->d_scratch + ((2 * p.nseg + 63) / 64 * 64);    // two length words per segment
-    return SIT_OK;
+    return wide_list_carve(c, p.nseg, p.seg_cap, &p.wcount, &p.wlist);
 }
 
 // sit_fill with assign = 1: the words of the fill and of the assignment behind it in ONE launch, ahead of the fill
@@ -619,22 +546,16 @@ int predict_reset_with_fill(sit_ctx *c, bool *done)
     return SIT_OK;
 }
 
-// the listed (wide) rows: packed columns in LDS where they fit, the split arrays in LDS, or global memory
-static int launch_wide_rows(sit_ctx *c, const PredArgs &a, i32 *wlist, unsigned *wcount, i64 seg_cap, int nseg, u64 *cnt)
+// the listed (wide) rows; cnt: count their labels (the narrow rows were counted by k_predict_rows_rec)
+static int launch_wide_rows(sit_ctx *c, const PredArgs &a, const PredPlan &p, u64 *cnt)
 {
-    const int ncu = c->num_cu > 0 ? c->num_cu : 256;
-    const size_t csc = (size_t)c->csc_nnz * 12 + (size_t)(c->D + 1) * 4 + 16;
-    const size_t rec = (size_t)c->csc_nrec * PRED_REC + (size_t)c->D * 4;
-    const char *pl = getenv("SITATOR_PREDICT_LDS"), *pr = getenv("SITATOR_PREDICT_REC");
-    const bool no_lds = pl && pl[0] == '0';
-    if (c->d_col_rec && rec <= 150 * 1024 && !no_lds && !(pr && pr[0] == '0')) {
-        HIP_TRY(c, lds_limit((const void *)k_predict_rows_wide_rec, rec, c->device));
-        k_predict_rows_wide_rec<<<dim3((unsigned)std::min(ncu, nseg)), dim3(PRED_WIDE_LDS_BLOCK), rec, c->stream>>>(a, c->d_col_rec, (int)c->csc_nrec, wlist, wcount, seg_cap, nseg, cnt);
-    } else if (csc <= 150 * 1024 && !no_lds) {
-        HIP_TRY(c, lds_limit((const void *)k_predict_rows_wide_lds, csc, c->device));
-        k_predict_rows_wide_lds<<<dim3((unsigned)std::min(ncu, nseg)), dim3(PRED_WIDE_LDS_BLOCK), csc, c->stream>>>(a, wlist, wcount, seg_cap, nseg, (int)c->csc_nnz, cnt);
+    const int ncu = cu_count(c);
+    if (p.wide_lds) {
+        HIP_TRY(c, lds_limit((const void *)k_predict_rows_wide_rec, p.wide_lds_bytes, c->device));
+        k_predict_rows_wide_rec<<<dim3((unsigned)std::min(ncu, p.nseg)), dim3(PRED_WIDE_LDS_BLOCK), p.wide_lds_bytes, c->stream>>>(
+            a, c->d_col_rec, (int)c->csc_nrec, p.wlist, p.wcount, p.seg_cap, p.nseg, cnt);
     } else
-        k_predict_rows_wide<<<dim3((unsigned)std::min(nseg, ncu * 8)), dim3(PRED_BLOCK), 0, c->stream>>>(a, wlist, wcount, seg_cap, nseg, cnt);
+        k_predict_rows_wide<<<dim3((unsigned)std::min(p.nseg, ncu * 8)), dim3(PRED_BLOCK), 0, c->stream>>>(a, p.wlist, p.wcount, p.seg_cap, p.nseg, cnt);
     return SIT_OK;
 }
 
@@ -660,47 +581,21 @@ static int run_predict(sit_ctx *c, double threshold, bool words_reset = false)
     a.N = c->rows_N; a.K = c->K; a.D = c->D; a.normed = c->centers_normed; a.threshold = threshold;
     SIT_REQUIRE(c, c->N < (1LL << 31), "sit_predict: more than 2^31 rows per context (the wide-row list holds 32-bit row numbers)");
     const unsigned grid = (unsigned)((c->N + PRED_BLOCK - 1) / PRED_BLOCK);
-    if (c->num_cu <= 0) {
-        int v = 0;
-        c->num_cu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0 ? v : 256;
-    }
     StageTimer t(c, T_PREDICT);
     bool counted = false;
     if (c->max_col <= PRED_MAXCOL) {
         PredPlan pp;
         if ((rc = predict_plan(c, pp))) return rc;
-        const bool narrow_lds = pp.narrow_lds, wide_lds = pp.wide_lds;
-        const int nt = pp.nt, nseg = pp.nseg;
-        const i64 seg_cap = pp.seg_cap;
-        const size_t lds = pp.lds;
-        unsigned *wcount = pp.wcount;
-        i32 *wlist = pp.wlist;
-        if (getenv("SITATOR_DEBUG_SHAPE")) fprintf(stderr, "predict: lds %zu nt %d per_cu %d nseg %d seg_cap %lld narrow_lds %d wide_lds %d rec %d rows_W %lld\n", lds, nt, pp.per_cu, nseg, (long long)seg_cap, (int)narrow_lds, (int)wide_lds, (int)pp.rec, (long long)c->rows_W);
-        u64 *cnt = narrow_lds ? (u64 *)c->d_counts : nullptr;            // the LDS kernel counts the labels on the way
+        if (getenv("SITATOR_DEBUG_SHAPE")) fprintf(stderr, "predict: lds %zu nt %d per_cu %d nseg %d seg_cap %lld narrow_lds %d wide_lds %d rows_W %lld\n", pp.lds, pp.nt, pp.per_cu, pp.nseg, (long long)pp.seg_cap, (int)pp.narrow_lds, (int)pp.wide_lds, (long long)c->rows_W);
         // sit_fill with assign = 1 has reset these words together with its own, ahead of the fill kernel
-        if (!words_reset && (rc = reset_predict_words(c, narrow_lds, wcount, 2 * nseg))) return rc;
-        if (narrow_lds && pp.rec) {
-            const int nrec = (int)c->csc_nrec;
-            if (nt == PRED_LDS_BLOCK) {
-                HIP_TRY(c, lds_limit((const void *)k_predict_rows_rec<PRED_LDS_BLOCK>, lds, c->device));
-                k_predict_rows_rec<PRED_LDS_BLOCK><<<dim3((unsigned)nseg), dim3(nt), lds, c->stream>>>(a, c->d_col_rec, nrec, wlist, wcount, seg_cap, (int)c->K, (u64 *)c->d_counts);
-            } else {
-                HIP_TRY(c, lds_limit((const void *)k_predict_rows_rec<1024>, lds, c->device));
-                k_predict_rows_rec<1024><<<dim3((unsigned)nseg), dim3(nt), lds, c->stream>>>(a, c->d_col_rec, nrec, wlist, wcount, seg_cap, (int)c->K, (u64 *)c->d_counts);
-            }
-            counted = true;
-        } else if (narrow_lds) {
-            if (nt == PRED_LDS_BLOCK) {
-                HIP_TRY(c, lds_limit((const void *)k_predict_rows_lds<PRED_LDS_BLOCK>, lds, c->device));
-                k_predict_rows_lds<PRED_LDS_BLOCK><<<dim3((unsigned)nseg), dim3(nt), lds, c->stream>>>(a, wlist, wcount, seg_cap, (int)c->csc_nnz, (int)c->K, (u64 *)c->d_counts);
-            } else {
-                HIP_TRY(c, lds_limit((const void *)k_predict_rows_lds<1024>, lds, c->device));
-                k_predict_rows_lds<1024><<<dim3((unsigned)nseg), dim3(nt), lds, c->stream>>>(a, wlist, wcount, seg_cap, (int)c->csc_nnz, (int)c->K, (u64 *)c->d_counts);
-            }
+        if (!words_reset && (rc = reset_predict_words(c, pp.narrow_lds, pp.wcount, 2 * pp.nseg))) return rc;
+        if (pp.narrow_lds) {                                              // the LDS kernel counts the labels on the way
+            HIP_TRY(c, lds_limit((const void *)k_predict_rows_rec, pp.lds, c->device));
+            k_predict_rows_rec<<<dim3((unsigned)pp.nseg), dim3(PRED_REC_BLOCK), pp.lds, c->stream>>>(a, c->d_col_rec, (int)c->csc_nrec, pp.wlist, pp.wcount, pp.seg_cap, (int)c->K, (u64 *)c->d_counts);
             counted = true;
         } else
-            k_predict_rows<<<dim3((unsigned)nseg), dim3(PRED_BLOCK), 0, c->stream>>>(a, wlist, wcount, seg_cap);
-        if (c->rows_W > 4 && (rc = launch_wide_rows(c, a, wlist, wcount, seg_cap, nseg, cnt))) return rc;
+            k_predict_rows<<<dim3((unsigned)pp.nseg), dim3(PRED_BLOCK), 0, c->stream>>>(a, pp.wlist, pp.wcount, pp.seg_cap);
+        if (c->rows_W > 4 && (rc = launch_wide_rows(c, a, pp, counted ? (u64 *)c->d_counts : nullptr))) return rc;
     } else k_predict_rows_dense<<<dim3(grid), dim3(PRED_BLOCK), 0, c->stream>>>(a);
     HIP_TRY(c, hipGetLastError());
     if (!counted && (rc = sit_label_counts(c))) return rc;      // np.bincount(labels[labels >= 0]) (:92)
@@ -719,8 +614,11 @@ int predict_listed_rows(sit_ctx *c, double threshold, i32 *wlist, unsigned *wcou
     a.col_ptr = c->d_col_ptr; a.col_k = c->d_col_k; a.col_val = c->d_col_val; a.dense = c->d_cen_dense;
     a.labels = c->d_labels; a.confs = c->d_confs;
     a.N = c->rows_N; a.K = c->K; a.D = c->D; a.normed = c->centers_normed; a.threshold = threshold;
+    PredPlan pp;
+    predict_form(c, pp);
+    pp.nseg = nseg; pp.seg_cap = seg_cap; pp.wcount = wcount; pp.wlist = wlist;
     StageTimer t(c, T_PREDICT);
-    { const int rcw = launch_wide_rows(c, a, wlist, wcount, seg_cap, nseg, nullptr); if (rcw) return rcw; }
+    { const int rcw = launch_wide_rows(c, a, pp, nullptr); if (rcw) return rcw; }
     HIP_TRY(c, hipGetLastError());
     int rc = sit_label_counts(c, false);
     if (rc) return rc;

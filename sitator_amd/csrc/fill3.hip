@@ -1406,15 +1406,9 @@ int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64
     i64 seg_cap = 0;
     if (fuse) {
         // rows left to k_predict_rows_wide*: listed in nseg segments of the scratch buffer, workgroup b into segment b % nseg
-        if (c->num_cu <= 0) {
-            int v = 0;
-            c->num_cu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0 ? v : 256;
-        }
-        nseg = (int)std::min<i64>((i64)grid_all > 0 ? (i64)grid_all : 1, (i64)c->num_cu * 4);
+        nseg = (int)std::min<i64>((i64)grid_all > 0 ? (i64)grid_all : 1, (i64)cu_count(c) * 4);
         seg_cap = ((i64)grid_all + nseg - 1) / nseg * ((i64)fpb * M);
-        if ((rc = ensure_scratch(c, ((i64)nseg * seg_cap + 2 * nseg + 64) * 4))) return rc;
-        a.wcount = (unsigned *)c->d_scratch;
-        a.wlist = (i32 *)c->d_scratch + ((2 * nseg + 63) / 64 * 64);
+        if ((rc = wide_list_carve(c, nseg, seg_cap, &a.wcount, &a.wlist))) return rc;
         a.seg_cap = seg_cap; a.nseg = nseg;
         a.col_ptr = c->d_col_ptr; a.col_k = c->d_col_k; a.col_val = c->d_col_val;
         a.labels = c->d_labels; a.confs = c->d_confs;

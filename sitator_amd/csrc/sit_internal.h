@@ -222,6 +222,16 @@ static inline int ensure_scratch(sit_ctx *c, i64 bytes)
     return SIT_OK;
 }
 
+// compute units of the context's device, queried once (256 when the query fails)
+static inline int cu_count(sit_ctx *c)
+{
+    if (c->num_cu <= 0) {
+        int v = 0;
+        c->num_cu = hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0 ? v : 256;
+    }
+    return c->num_cu;
+}
+
 // HIP-event time of a stage on the context's stream.  stop() only records: the elapsed time is read when the timers
 // are queried (sit_timers) or the slot is reused, so timing a stage costs no host synchronisation.
 static inline void stage_timer_resolve(sit_ctx *c, int slot)
@@ -472,6 +482,9 @@ bool fill3_eligible(sit_ctx *c);
 // frames [f_lo, f_hi); fuse: assign the narrow rows in the same kernel (needs centres; *fused says whether it did - if
 // not, the rows were stored whatever `store` says and the caller runs the assignment kernels)
 int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo = 0, i64 f_hi = -1, bool fuse = false, bool *fused = nullptr);
+// cluster.hip: the wide-row list in the scratch buffer - two length words per segment, then from the next 64-word
+// boundary nseg segments of seg_cap rows
+int wide_list_carve(sit_ctx *c, int nseg, i64 seg_cap, unsigned **wcount, i32 **wlist);
 // cluster.hip: the rows k_fill3 listed (segments of the scratch buffer), then the label counts
 int predict_listed_rows(sit_ctx *c, double threshold, i32 *wlist, unsigned *wcount, i64 seg_cap, int nseg);
 int download_staged(sit_ctx *c, hipStream_t stream, void *dst, const void *src, size_t bytes);   // fill.hip: large read-backs

@@ -1,5 +1,5 @@
-"""Soak script (not collected by pytest): random centre sets and rows through the three forms of the assignment kernel
-(packed columns in LDS, split arrays in LDS, global memory) and the oracle.  python tests/soak_predict.py [n]  (FUZZ_BASE=<first seed>)"""
+"""Soak script (not collected by pytest): random centre sets and rows through the two forms of the assignment kernel
+(packed columns in LDS, global memory) and the oracle.  python tests/soak_predict.py [n]  (FUZZ_BASE=<first seed>)"""
 import sys, os, time
 os.environ.setdefault("SITATOR_PROGRESSBAR", "false")
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -48,7 +48,7 @@ for it in range(n):
     for thr in (0.0, float(rng.choice([0.3, 0.45, 0.8, 0.99]))):
         lab_o, conf_o = oracle.predict(X, centers, thr, normed)
         got = {}
-        for name, var in (("packed", None), ("split", "SITATOR_PREDICT_REC"), ("global", "SITATOR_PREDICT_LDS")):
+        for name, var in (("packed", None), ("global", "SITATOR_PREDICT_LDS")):
             if var:
                 os.environ[var] = "0"
             try:
@@ -56,8 +56,7 @@ for it in range(n):
             finally:
                 if var:
                     os.environ.pop(var, None)
-        for name in ("split", "global"):
-            ok = ok and all(np.array_equal(a, b) for a, b in zip(got["packed"], got[name]))
+        ok = ok and all(np.array_equal(a, b) for a, b in zip(got["packed"], got["global"]))
         lab, conf, cnt = got["packed"]
         ok = ok and np.array_equal(lab, lab_o) and np.allclose(conf, conf_o, rtol=1e-12, atol=0) \
             and np.array_equal(cnt, np.bincount(lab[lab >= 0], minlength=K))

@@ -296,7 +296,7 @@ def test_deferred_fill_reports_through_fill_result():
 
 @pytest.mark.parametrize("cfg,M,F", [("C2", 64, 400), ("C5", 160, 120)])
 def test_predict_with_centres_in_lds_equals_predict_from_global_memory(oracle, cfg, M, F):
-    """The site assignment keeps the centres' CSC arrays in LDS when they fit and counts the labels on the way; the
+    """The site assignment keeps the centres' packed columns in LDS when they fit and counts the labels on the way; the
     kernels that read them from global memory (larger centre sets) must give the same labels, confidences and
     counts - narrow rows (C2) and rows wide enough for the wide-row kernel (C5)."""
     from sitator_amd import synth
@@ -306,14 +306,13 @@ def test_predict_with_centres_in_lds_equals_predict_from_global_memory(oracle, c
     X = ctx.rows_dense()
     centers = oracle.fit_centers(X, 0.45)
     ctx.set_centers(centers / np.linalg.norm(centers, axis=1)[:, None], True)
-    lab_a, conf_a, cnt_a = ctx.predict(0.8)                  # packed columns in LDS (round 5)
-    for var in ("SITATOR_PREDICT_LDS", "SITATOR_PREDICT_REC"):   # global memory; the split arrays in LDS
-        os.environ[var] = "0"
-        try:
-            lab_b, conf_b, cnt_b = ctx.predict(0.8)
-        finally:
-            os.environ.pop(var, None)
-        assert np.array_equal(lab_a, lab_b) and np.array_equal(conf_a, conf_b) and np.array_equal(cnt_a, cnt_b), var
+    lab_a, conf_a, cnt_a = ctx.predict(0.8)                  # packed columns in LDS
+    os.environ["SITATOR_PREDICT_LDS"] = "0"                   # global memory
+    try:
+        lab_b, conf_b, cnt_b = ctx.predict(0.8)
+    finally:
+        os.environ.pop("SITATOR_PREDICT_LDS", None)
+    assert np.array_equal(lab_a, lab_b) and np.array_equal(conf_a, conf_b) and np.array_equal(cnt_a, cnt_b)
     assert np.array_equal(cnt_a, np.bincount(lab_a[lab_a >= 0], minlength=len(centers)))
     lab_o, conf_o = oracle.predict(X, centers, 0.8, True)
     assert np.array_equal(lab_o, lab_a)
@@ -321,12 +320,12 @@ def test_predict_with_centres_in_lds_equals_predict_from_global_memory(oracle, c
 
 @pytest.mark.parametrize("normed,nonfinite", [(True, False), (False, False), (True, True)])
 def test_assignment_kernels_agree_on_ties_nans_and_every_row_width(oracle, normed, nonfinite):
-    """The three forms of the assignment (packed columns in LDS, split arrays in LDS, global memory) and the oracle
+    """The two forms of the assignment (packed columns in LDS, global memory) and the oracle
     (util/DotProdClassifier.pyx:129-197: np.argmax of |centres . x| - the first maximum, the first NaN) on rows made to
     meet every branch: exact ties between centres, quotients that differ in the last place only (the reference divides by
     |x| BEFORE it compares), negative products, centres that do not overlap the row, rows of 0-4 entries (the narrow
     kernel), 5-16 (the wide merges) and more (the generic one), thresholds on both sides.  With NaN / infinite centre
-    entries (nonfinite) the three forms are compared with each other only: the reference's DENSE product turns such a
+    entries (nonfinite) the two forms are compared with each other only: the reference's DENSE product turns such a
     centre's score into NaN for every row (0 x NaN), which no fitted centre set produces and the sparse kernels do not
     reproduce for rows outside the entry's landmark."""
     from sitator_amd import _lib
@@ -367,7 +366,7 @@ def test_assignment_kernels_agree_on_ties_nans_and_every_row_width(oracle, norme
         with np.errstate(invalid="ignore", over="ignore"):
             lab_o, conf_o = oracle.predict(X, centers, thr, normed)
         got = {}
-        for name, var in (("packed", None), ("split", "SITATOR_PREDICT_REC"), ("global", "SITATOR_PREDICT_LDS")):
+        for name, var in (("packed", None), ("global", "SITATOR_PREDICT_LDS")):
             if var:
                 os.environ[var] = "0"
             try:
@@ -375,9 +374,8 @@ def test_assignment_kernels_agree_on_ties_nans_and_every_row_width(oracle, norme
             finally:
                 if var:
                     os.environ.pop(var, None)
-        for name in ("split", "global"):
-            for a, b in zip(got["packed"], got[name]):
-                assert np.array_equal(a, b, equal_nan=True), (name, thr)
+        for a, b in zip(got["packed"], got["global"]):
+            assert np.array_equal(a, b, equal_nan=True), thr
         lab, conf, cnt = got["packed"]
         assert np.array_equal(cnt, np.bincount(lab[lab >= 0], minlength=K))
         if not nonfinite:
