@@ -227,12 +227,10 @@ def predict_csr(csr, D, centers, threshold, normed=True):
     return labels, confs
 
 
-def cluster_dotprod_csr(csr, D, params, min_samples):
-    """landmark/cluster/dotprod.py:11-33 + fit_predict (:68-127) on CSR rows."""
-    p = {"clustering_threshold": 0.45, "assignment_threshold": 0.8}
-    p.update(params)
-    centers = fit_centers_csr(csr, D, p["clustering_threshold"])
-    labels, confs = predict_csr(csr, D, centers, p["assignment_threshold"], True)
+def _cluster_dotprod_from_centers(centers, predict_all, params, min_samples):
+    """fit_predict (:68-127) after the fit: assign, the ``min_samples`` filter, assign again.  ``predict_all(centers,
+    threshold)`` assigns every row and returns (labels, confs)."""
+    labels, confs = predict_all(centers, params["assignment_threshold"])
     n_assigned = int(np.sum(labels >= 0))
     counts = np.bincount(labels[labels >= 0], minlength=len(centers))
     ms = int(min_samples) if isinstance(min_samples, (int, np.integer)) else int(np.floor(min_samples * n_assigned))
@@ -240,9 +238,45 @@ def cluster_dotprod_csr(csr, D, params, min_samples):
     centers, counts = centers[mask], counts[mask]
     if len(centers) == 0:
         raise OracleError("ValueError", what="`min_samples` too large")
-    labels, confs = predict_csr(csr, D, centers, p["assignment_threshold"], True)
+    labels, confs = predict_all(centers, params["assignment_threshold"])
     return {"cluster-size": counts, "cluster-labels": labels, "cluster-confs": confs,
             "cluster-representative-lvecs": centers}
+
+
+def cluster_dotprod_csr(csr, D, params, min_samples):
+    """landmark/cluster/dotprod.py:11-33 + fit_predict (:68-127) on CSR rows."""
+    p = {"clustering_threshold": 0.45, "assignment_threshold": 0.8}
+    p.update(params)
+    centers = fit_centers_csr(csr, D, p["clustering_threshold"])
+    return _cluster_dotprod_from_centers(centers, lambda cen, thr: predict_csr(csr, D, cen, thr, True), p, min_samples)
+
+
+def fill_csr_blocks(cell, frames, static_idx, mobile_idx, ref_static, verts, vcd, check_for_zeros=True, block=256,
+                    map_fn=map):
+    """``fill`` of consecutive ``block``-frame cuts of an unwrapped trajectory, each made sparse: [(csr, n_all_zero)]
+    in frame order.  ``map_fn`` may be a thread pool's ``map`` (the C loop releases the GIL)."""
+    def one(lo):
+        lv, nz = fill(cell, wrap_points(cell, frames[lo:lo + block]), static_idx, mobile_idx, ref_static, verts, vcd,
+                      check_for_zeros=check_for_zeros)
+        return to_csr(lv), nz
+    return list(map_fn(one, range(0, len(frames), block)))
+
+
+def cluster_dotprod_csr_blocks(blocks, D, params, min_samples, map_fn=map):
+    """``cluster_dotprod_csr`` over consecutive CSR row blocks: the fit streams all rows in order (serial by nature),
+    every assignment runs per block through ``map_fn`` (e.g. a thread pool's ``map``; the C loops release the GIL) and
+    the blocks' results are concatenated.  Rows are assigned independently, so the result is that of
+    ``cluster_dotprod_csr(csr_concat(blocks), ...)`` bit for bit."""
+    p = {"clustering_threshold": 0.45, "assignment_threshold": 0.8}
+    p.update(params)
+    blocks = list(blocks)
+    centers = fit_centers_csr(csr_concat(blocks), D, p["clustering_threshold"])
+
+    def predict_all(cen, thr):
+        parts = list(map_fn(lambda b: predict_csr(b, D, cen, thr, True), blocks))
+        return np.concatenate([q[0] for q in parts]), np.concatenate([q[1] for q in parts])
+
+    return _cluster_dotprod_from_centers(centers, predict_all, p, min_samples)
 
 
 def fit_predict(X, threshold, min_samples, predict_threshold=None, predict_normed=True,
@@ -476,7 +510,8 @@ def jump_analysis(traj, n_sites):
     with np.errstate(divide="ignore", invalid="ignore"):
         p_ij = n_ij / total
     return {"n_ij": n_ij, "p_ij": p_ij, "jump_lag": lag, "residence_times": res,
-            "occupancy_freqs": np.sum(n_ij, axis=0) / F, "total_corrected_residences": total, "n_problems": problems}
+            "occupancy_freqs": np.sum(n_ij, axis=0) / F, "total_corrected_residences": total, "n_problems": problems,
+            "time_sum": tsum, "time_n": tn}
 
 
 def assign_to_last_known_site(traj, frame_threshold=1):

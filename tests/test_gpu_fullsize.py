@@ -1,5 +1,6 @@
 """GPU, BASELINE.json full size (config C2: 100 000 frames x 64 mobile ions = 6.4e6 landmark vectors):
-size-independent properties plus oracle parity on a random sample of frames."""
+size-independent properties, oracle parity on a random sample of frames, the whole run against the oracle's stream, and
+the label-trajectory operators on the run's labels against the oracle."""
 import numpy as np
 import pytest
 
@@ -110,6 +111,104 @@ def test_full_size_two_shards_equal_one_pass(c2_full):
         c.set_centers(normed, True)
         labels.append(c.predict(0.8)[0])
     assert np.array_equal(np.concatenate(labels).reshape(100000, 64), st.traj)
+
+
+def test_c2_full_size_run_equals_the_oracle_stream(c2_full, oracle):
+    """The whole C2 run at its stated size against the ORACLE, not against the product's other paths: the oracle fills
+    the 100 000 frames (256-frame blocks on a thread pool), streams the 6.4e6 sparse rows through its CSR fit (serial by
+    nature) and assigns them per block.  Labels, sizes and the all-zero count must be identical, fitted centres and
+    confidences within the float bar of the 12 288-frame test, site centres within the sharded golden test's bar, the
+    occupancy statistics equal."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    from tests.test_gpu_parity import RTOL
+    host, gen, ref, frames, sn, la, st = c2_full
+    F, M = st.traj.shape
+    sidx, midx = np.where(gen.static_mask)[0], np.where(gen.mobile_mask)[0]
+    verts, vcd = oracle.site_vertex_distances(host.cell, host.centers, host.vertices, ref[sidx])
+    D = len(host.centers)
+    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as ex:
+        parts = oracle.fill_csr_blocks(host.cell, frames, sidx, midx, ref[sidx], verts, vcd,
+                                       check_for_zeros=la.check_for_zero_landmarks, block=256, map_fn=ex.map)
+        out = oracle.cluster_dotprod_csr_blocks([p[0] for p in parts], D, {}, 0.01 / M, map_fn=ex.map)
+    n_zero = sum(p[1] for p in parts)
+    del parts
+    labels = out["cluster-labels"].reshape(F, M)
+    confs = out["cluster-confs"].reshape(F, M)
+    K = len(out["cluster-size"])
+    assert la.n_all_zero_lvecs == n_zero
+    assert np.mean(labels < 0) > 0, "the run must hold unassigned samples"
+    assert np.array_equal(st.traj, labels), "site indices must be identical to the oracle's"
+    assert st.site_network.n_sites == K
+    assert np.array_equal(np.bincount(st.traj[st.traj >= 0], minlength=K), out["cluster-size"])
+    np.testing.assert_allclose(np.asarray(la.cluster_centers_), out["cluster-representative-lvecs"], rtol=1e-9, atol=1e-300)
+    m = labels >= 0
+    np.testing.assert_allclose(st.confidences[m], confs[m], rtol=RTOL)
+    # site centres (real-weighted, LandmarkAnalysis.py:278-287): the oracle's average of every site's wrapped mobile
+    # positions, weighted by the oracle's confidences; rows grouped by label once, in row order
+    mob = oracle.wrap_points(host.cell, frames[:, midx]).reshape(-1, 3)
+    flat = labels.reshape(-1)
+    order = np.argsort(flat, kind="stable")
+    bounds = np.searchsorted(flat[order], np.arange(K + 1))
+    w = confs.reshape(-1)
+    exp_centers = np.empty((K, 3))
+    for s in range(K):
+        rows = order[bounds[s]:bounds[s + 1]]
+        exp_centers[s] = oracle.average(host.cell, mob[rows], w[rows])
+    np.testing.assert_allclose(np.asarray(st.site_network.centers), exp_centers, rtol=1e-6, atol=1e-8)
+    n_multi, avg = oracle.check_multiple_occupancy(labels, K, 1)
+    assert la.n_multiple_assignments == n_multi and la.avg_mobile_per_site == avg
+
+
+def test_c2_full_size_label_trajectory_layer_equals_the_oracle(c2_full, oracle):
+    """The label-trajectory operators (JumpAnalysis, jumps, assign_to_last_known_site, occupancies, running windowed
+    mode) on the full-size C2 labels - 391 frame chunks of the device scans - against the oracle.  Every operator runs
+    on a fresh trajectory around a copy of the labels (assign_to_last_known_site rewrites its labels in place and the
+    fixture is shared)."""
+    from sitator_amd import JumpAnalysis, SmoothSiteTrajectory
+    from tests.test_next_tier import JA, _eq, _st
+    host, gen, ref, frames, sn, la, st = c2_full
+    lab0 = np.array(st.traj, copy=True)
+    F, M = lab0.shape
+    K = st.site_network.n_sites
+    # JumpAnalysis: the site / edge attributes, and the raw accumulators (n_problems is only logged by the operator)
+    exp = oracle.jump_analysis(lab0, K)
+    got = JumpAnalysis().run(_st(lab0.copy(), K))
+    for a in JA:
+        assert _eq(getattr(got.site_network, a), exp[a]), a
+    n_ij, tsum, tn, total, nprob, _, _ = _st(lab0.copy(), K)._device().jump_analysis(K)
+    assert np.array_equal(n_ij, exp["n_ij"]) and np.array_equal(total, exp["total_corrected_residences"])
+    assert np.array_equal(tsum, exp["time_sum"]) and np.array_equal(tn, exp["time_n"])
+    assert nprob == exp["n_problems"]
+    assert exp["n_ij"].sum() - np.trace(exp["n_ij"]) > 1000, "the run must hold jumps"
+    # jumps
+    assert list(_st(lab0.copy(), K).jumps()) == oracle.jumps(lab0)
+    # assign_to_last_known_site
+    for thr in (1, 3):
+        s2 = _st(lab0.copy(), K)
+        res = s2.assign_to_last_known_site(frame_threshold=thr)
+        t, (mx, avg, re) = oracle.assign_to_last_known_site(lab0, thr)
+        assert np.array_equal(s2.traj, t)
+        assert res["max_time_unknown"] == mx and res["total_reassigned"] == re
+        assert res["avg_time_unknown"] == pytest.approx(avg, rel=1e-15, abs=0)
+    # occupancies
+    occ = _st(lab0.copy(), K).compute_site_occupancies()
+    assert np.array_equal(occ, np.true_divide(np.bincount(lab0[lab0 >= 0], minlength=K), F))
+    # running windowed mode on three frame bands (the oracle's loop is too slow for 6.4e6 labels); the window is local,
+    # so the oracle sees every band with a margin of wleft + wright frames and the interior is compared
+    mid = 256 * (F // 512)
+    bands = [(0, 320), (mid - 160, mid + 160), (F - 320, F)]
+    for thr, factor, repl in ((3, 2.1, True), (5, 2.1, False)):
+        w = factor * thr
+        wl, wr = int(np.floor(w / 2)), int(np.ceil(w / 2))
+        sm = SmoothSiteTrajectory(window_threshold_factor=factor, remove_unoccupied_sites=False,
+                                  set_unassigned_under_threshold=repl)
+        out = sm.run(_st(lab0.copy(), K), thr).traj
+        for lo, hi in bands:
+            a, b = max(lo - wl - wr, 0), min(hi + wl + wr, F)
+            e = oracle.running_windowed_mode(lab0[a:b], wl, wr, thr, K, repl)
+            assert np.array_equal(out[lo:hi], e[lo - a:hi - a]), (thr, lo)
+    assert np.array_equal(st.traj, lab0), "the fixture's labels must be untouched"
 
 
 @pytest.mark.parametrize("cfg,M,F", [("C3", 448, 250000), ("C4", 256, 125000)])

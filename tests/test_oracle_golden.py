@@ -196,3 +196,35 @@ def test_sparse_markov_clustering_equals_dense(oracle, n, seed):
         mine = markov.markov_clustering(A, inflation=inflation)
         ref = oracle.markov_clustering(A, inflation=inflation)
         assert [tuple(g) for g in mine] == [tuple(int(x) for x in g) for g in ref]
+
+
+def test_block_parallel_dotprod_equals_the_serial_one(oracle):
+    """`cluster_dotprod_csr_blocks` (the oracle stream of the full-size GPU test: assignments per row block on a thread
+    pool) gives `cluster_dotprod_csr`'s labels, confidences, centres and sizes bit for bit, on a C2 cut of 4096 frames
+    cut into uneven blocks."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    from sitator_amd import synth
+    host = synth.config_host("C2")
+    gen = synth.TrajectoryGenerator(host, 64, seed=2)
+    frames = gen.generate(4096)
+    ref = gen.reference_positions()
+    sidx, midx = np.where(gen.static_mask)[0], np.where(gen.mobile_mask)[0]
+    verts, vcd = oracle.site_vertex_distances(host.cell, host.centers, host.vertices, ref[sidx])
+    D = len(host.centers)
+    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as ex:
+        parts = oracle.fill_csr_blocks(host.cell, frames, sidx, midx, ref[sidx], verts, vcd, block=256, map_fn=ex.map)
+        blocks = [p[0] for p in parts]
+        whole = oracle.csr_concat(blocks)
+        # regroup into uneven blocks (row counts not a multiple of anything the serial path sees)
+        cuts = [0, 1, 64 * 37 + 5, 64 * 1000, 64 * 2048 + 63, len(whole[0]) - 1]
+        uneven = []
+        for lo, hi in zip(cuts[:-1], cuts[1:]):
+            ip = whole[0][lo:hi + 1]
+            uneven.append((ip - ip[0], whole[1][ip[0]:ip[-1]], whole[2][ip[0]:ip[-1]]))
+        exp = oracle.cluster_dotprod_csr(whole, D, {}, 0.01 / 64.0)
+        for bl in (blocks, uneven):
+            got = oracle.cluster_dotprod_csr_blocks(bl, D, {}, 0.01 / 64.0, map_fn=ex.map)
+            for key in ("cluster-labels", "cluster-confs", "cluster-representative-lvecs", "cluster-size"):
+                assert got[key].dtype == exp[key].dtype and np.array_equal(got[key], exp[key]), key
+    assert np.mean(exp["cluster-labels"] < 0) > 0 and len(exp["cluster-size"]) >= 64
