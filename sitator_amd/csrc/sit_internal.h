@@ -456,11 +456,16 @@ __device__ __forceinline__ void exact_add(u64 *hi, u64 *lo, double v)
     exact_flush(hi, lo, xhi, xlo);
 }
 
-// (hi, lo) of exact_add as a double: two roundings (the low word's conversion and the final sum), both deterministic
+// (hi, lo) of exact_add as a double: two roundings (the low word's conversion and the final sum), both deterministic.
+// A negative accumulator is converted by its magnitude and negated: taken as it stands, a small negative sum has
+// hi = -1 and lo just below 2^64, (double)lo rounds to 2^64 and the two terms cancel (-2^-70 came back as 0).
 __host__ __device__ inline double exact_value(u64 hi, u64 lo)
 {
-    const double h = ldexp((double)(long long)hi, -16);   // signed high word
-    return h + ldexp((double)lo, -80);
+    const bool neg = (long long)hi < 0;
+    if (neg) { lo = ~lo + 1ull; hi = ~hi + (lo == 0 ? 1ull : 0ull); }
+    const double h = ldexp((double)(long long)hi, -16);   // high word (of the magnitude)
+    const double v = h + ldexp((double)lo, -80);
+    return neg ? -v : v;
 }
 
 // host-side pieces implemented in other translation units

@@ -467,7 +467,14 @@ def exact_sum_across(comm, hi, lo):
         lo = (s_l0 & m32) | ((mid & m32) << np.uint64(32))
         with np.errstate(over="ignore"):
             hi = s_hi + (mid >> np.uint64(32))
-    return np.ldexp(hi.view(np.int64).astype(np.float64), -16) + np.ldexp(lo.astype(np.float64), -80)
+    # a negative accumulator: its magnitude converted, then negated (as exact_value: the two terms of a small negative
+    # sum taken as they stand cancel)
+    neg = hi.view(np.int64) < 0
+    one = np.uint64(1)
+    lo_m = np.where(neg, ~lo + one, lo)
+    hi_m = np.where(neg, ~hi + (lo_m == 0).astype(np.uint64), hi)
+    v = np.ldexp(hi_m.view(np.int64).astype(np.float64), -16) + np.ldexp(lo_m.astype(np.float64), -80)
+    return np.where(neg, -v, v)
 
 
 def shard_frames(n_frames, rank, size):

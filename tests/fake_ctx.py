@@ -217,6 +217,14 @@ class FakeContext(object):
         return np.dot(self.X.T, self.X), np.count_nonzero(self.X, axis=0).astype(np.int64)
 
     def best_match(self, c):
+        c = np.asarray(c, dtype=np.float64)
+        if not np.all(np.isfinite(c)):
+            # the device holds a row's non-zeros only: the exact zeros of a row never meet a NaN or an infinity of
+            # the centre (tests/test_gpu_reductions.py compares this double with the device)
+            with np.errstate(invalid="ignore"):
+                proj = np.abs(np.where(self.X != 0, self.X * c[None, :], 0.0).sum(axis=1))
+            row = _argmax_np(proj)
+            return row, float(proj[row]), float(np.linalg.norm(self.X[row]))
         proj = np.abs(np.dot(self.X, c))
         row = _argmax_np(proj)
         return row, float(np.abs(np.dot(self.X[row], c))), float(np.linalg.norm(self.X[row]))
