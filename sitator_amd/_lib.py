@@ -678,8 +678,8 @@ class HipContext(object):
         return {k: (float(t[8 + i]), int(t[16 + i])) for i, k in enumerate(names)}
 
     def info(self):
-        v = np.zeros(28)
-        self.lib.sit_info(self._h, _d(v), 28)
+        v = np.zeros(29)
+        self.lib.sit_info(self._h, _d(v), 29)
         keys = ["row_width", "mean_candidates_loose", "tight_width", "mean_candidates_tight", "delta",
                 "fallback_frames"]
         out = dict(zip(keys, v[:6]))
@@ -693,6 +693,7 @@ class HipContext(object):
         out["assignment_fused"] = bool(v[22])
         out["band_redos"] = int(v[23])
         out["census"] = [float(x) for x in v[24:28]]
+        out["fill_slot_width"] = int(v[28])
         return out
 
     def synchronize(self):

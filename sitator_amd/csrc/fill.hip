@@ -681,7 +681,7 @@ extern "C" int sit_fill(sit_ctx *c, const sit_fill_params *p, i64 *n_all_zero, s
             StageTimer timer(c, T_FILL);
             if (p->dynamic_lattice_mapping && (rc = launch_lattice_map(c, p))) return rc;
             if (v3) rc = fill3_launch(c, p, store, 0, -1, want_fuse, &fused);
-            else { c->last_kernel = 1; c->last_fused = false; rc = launch_fill_v1(c, p); }
+            else { c->last_kernel = 1; c->last_fused = false; c->last_slot = 0; rc = launch_fill_v1(c, p); }
             if (rc) return rc;
             timer.stop();
         }

@@ -21,6 +21,13 @@
 //     one, r = the end-of-list bits below the task in the pass's 64-bit mask: two mbcnt -, loads its list entry - 16 bytes: the landmark's CRITICAL vertex (the vertex with the least room
 //     in the ion's bin, from the table builder), that vertex's LDS offset and its exact threshold - and tests that
 //     vertex; what passes is compacted into the wave's task table with a ballot;
+//   * the SLOT form of that stage (one frame per workgroup; the default where the primary table has no list of more than
+//     eight entries and the workgroup has four waves - C2): no task space at all.  A D0 lane is (ion of the pass, slot of
+//     its list) by its number - eight slots per ion, eight ions a pass -, reads its ion's {first entry, entries} from
+//     ioninfo[] and loads entry `slot` if the list is that long: no prefix sum, no end-of-list marks, no per-list records,
+//     one LDS read in front of the entry's load.  The tasks still come out ion-major, ascending landmark, so everything
+//     from the task table on is the same.  A frame whose ions met a longer list (phase 1b leaves the length in LDS) runs
+//     16, 32 or 64 slots per ion in all its windows; a frame on the fallback table looks its lists up per window first;
 //   * the remaining tasks take (task, vertex) LANES: eight lanes per task, one squared distance each, compared with
 //     the EXACT squared-distance threshold of (landmark, vertex): the largest double d2 for which the reference's
 //     RN(RN(sqrt(d2)) / vcd) > cutoff is false, found on the host by bisection over the doubles (sqrt and the division
@@ -343,36 +350,63 @@ __device__ __forceinline__ int bin_of3(const Pbc &P, double px, double py, doubl
         }                                                                                                                  \
     } while (0)
 
-// NP0 passes of D0 from task `base` on: a lane per candidate task - its list (the number of end-of-list bits below it), its
-// list entry, the CRITICAL vertex of (bin, landmark) tested; the tasks that pass are appended to the task table.  The
-// entries of all NP0 passes are requested before the first is used.
-#define F3_D0_PASSES(NP0)                                                                                                  \
-    do {                                                                                                                   \
-        uint4 en_[NP0];                                                                                                    \
-        unsigned ionoff_[NP0], statoff_[NP0], tfl_[NP0];                                                                   \
-        int ion_[NP0];                                                                                                     \
-        unsigned long long vmask_[NP0];                                                                                    \
-        _Pragma("unroll") for (int u = 0; u < NP0; u++) {                                                                  \
-            const int b_ = base + 64 * u, t = b_ + lane;                                                                   \
-            vmask_[u] = first_lanes(nlt0 - b_);                                                                            \
-            const uint2 mw = *(const uint2 *)(mark + (b_ >> 5));                  /* (one address for the wave) */          \
-            const unsigned m_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)mw.x), m_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)mw.y); \
-            const unsigned rk = __builtin_amdgcn_mbcnt_hi(m_hi, __builtin_amdgcn_mbcnt_lo(m_lo, (unsigned)carry));         \
-            carry += __builtin_popcount(m_lo) + __builtin_popcount(m_hi);                                                  \
-            en_[u] = make_uint4(0u, 0u, 0u, 0x7ff00000u);         /* an idle lane: landmark 0, static 0, threshold +inf */  \
-            statoff_[u] = 0u; tfl_[u] = 0u;                                                                                \
-            if (FPB1) {                                                                                                    \
-                const uint2 rr = ((const uint2 *)ionrec)[rk];                                                              \
-                ion_[u] = (int)rr.y;                                                                                       \
-                if (F3_LANES(vmask_[u])) en_[u] = pack[rr.x + (unsigned)t];                                                \
-                ionoff_[u] = ionbase + 24u * (unsigned)ion_[u];                                                            \
-            } else {                                                                                                       \
-                ion_[u] = (int)rk2ion[rk];                                                                                 \
-                const uint4 ir = ((const uint4 *)ionrec)[ion_[u]];                                                         \
-                if (F3_LANES(vmask_[u])) en_[u] = pack[ir.x + (unsigned)t];                                                \
-                ionoff_[u] = ir.y; statoff_[u] = ir.z; tfl_[u] = ir.w;                                                     \
-            }                                                                                                              \
-        }                                                                                                                  \
+// NP0 passes of D0 from `base` on; the tasks that pass the test of their CRITICAL vertex of (bin, landmark) are appended to
+// the task table.  The entries of all NP0 passes are requested before the first is used.
+//   flat form: `base` is a task, a lane per candidate task - its list (the number of end-of-list bits below it), its list entry;
+//   slot form (SLOT): `base` is an ion of the window, a lane per (ion, slot of its list): d0_step ions of 64 / d0_step slots a pass.
+// Both take the tasks in the same order (ion-major, ascending landmark within a list).
+#define F3_D0_PASSES(NP0)                                                                                                   \
+    do {                                                                                                                    \
+        uint4 en_[NP0];                                                                                                     \
+        unsigned ionoff_[NP0], statoff_[NP0], tfl_[NP0];                                                                    \
+        int ion_[NP0];                                                                                                      \
+        unsigned long long vmask_[NP0];                                                                                     \
+        uint2 ii_[NP0];                                                                                                     \
+        bool in_[NP0];                                                                                                      \
+        if (SLOT) {                                                                                                         \
+            /* my ion (of the window) and my slot of its list follow from the lane: one LDS read before the entry.  A lane */ \
+            /* beyond the window's last ion reads LDS behind the ions' records and offset vectors (inside the workgroup's */ \
+            /* allocation: the exp table and the waves' regions follow) and is masked out */                                \
+            _Pragma("unroll") for (int u = 0; u < NP0; u++) {                                                               \
+                ion_[u] = base + d0_step * u + s_ion;                                                                       \
+                in_[u] = ion_[u] < nib;                                                                                     \
+                ii_[u] = ioninfo[ib0 + ion_[u]];                                                                            \
+                ionoff_[u] = ionbase + 24u * (unsigned)(base + d0_step * u) + s_ioff;                                       \
+            }                                                                                                               \
+            /* (the empty asm statements order the issue: the reads of all passes, then the loads of all passes) */         \
+            _Pragma("unroll") for (int u = 0; u < NP0; u++) asm volatile("" : "+v"(ii_[u].x), "+v"(ii_[u].y));              \
+        }                                                                                                                   \
+        _Pragma("unroll") for (int u = 0; u < NP0; u++) {                                                                   \
+            statoff_[u] = 0u; tfl_[u] = 0u;                                                                                 \
+            if (SLOT) {                                                                                                     \
+                /* The load is unconditional (a branch round it made the compiler wait for each pass's entry where it was */ \
+                /* issued): an idle lane reads entry 0 - a valid landmark and static atom - and is masked out of the ballot */ \
+                const bool act_ = in_[u] && s_slot < (int)(ii_[u].y & 255u);                                                \
+                vmask_[u] = __ballot(act_);                                                                                 \
+                en_[u] = pack[act_ ? ii_[u].x + (unsigned)s_slot : 0u];                                                     \
+            } else {                                                                                                        \
+                en_[u] = make_uint4(0u, 0u, 0u, 0x7ff00000u);     /* an idle lane: landmark 0, static 0, threshold +inf */  \
+                const int b_ = base + 64 * u, t = b_ + lane;                                                                \
+                vmask_[u] = first_lanes(nlt0 - b_);                                                                         \
+                const uint2 mw = *(const uint2 *)(mark + (b_ >> 5));              /* (one address for the wave) */          \
+                const unsigned m_lo = (unsigned)__builtin_amdgcn_readfirstlane((int)mw.x), m_hi = (unsigned)__builtin_amdgcn_readfirstlane((int)mw.y); \
+                const unsigned rk = __builtin_amdgcn_mbcnt_hi(m_hi, __builtin_amdgcn_mbcnt_lo(m_lo, (unsigned)carry));      \
+                carry += __builtin_popcount(m_lo) + __builtin_popcount(m_hi);                                               \
+                if (FPB1) {                                                                                                 \
+                    const uint2 rr = ((const uint2 *)ionrec)[rk];                                                           \
+                    ion_[u] = (int)rr.y;                                                                                    \
+                    if (F3_LANES(vmask_[u])) en_[u] = pack[rr.x + (unsigned)t];                                             \
+                    ionoff_[u] = ionbase + 24u * (unsigned)ion_[u];                                                         \
+                } else {                                                                                                    \
+                    ion_[u] = (int)rk2ion[rk];                                                                              \
+                    const uint4 ir = ((const uint4 *)ionrec)[ion_[u]];                                                      \
+                    if (F3_LANES(vmask_[u])) en_[u] = pack[ir.x + (unsigned)t];                                             \
+                    ionoff_[u] = ir.y; statoff_[u] = ir.z; tfl_[u] = ir.w;                                                  \
+                }                                                                                                           \
+            }                                                                                                               \
+        }                                                                                                                   \
+        /* (keeps an entry one 16-byte load: left alone the compiler fetches its first word again, behind the test) */      \
+        if (SLOT) { _Pragma("unroll") for (int u = 0; u < NP0; u++) asm volatile("" : "+v"(en_[u].x)); }                    \
         _Pragma("unroll") for (int u = 0; u < NP0; u++) {                                                                  \
             const uint4 en = en_[u];                                                                                       \
             unsigned voff = en.y;                                                                                          \
@@ -634,9 +668,11 @@ __device__ __forceinline__ double dpp_row_shl(double x)
 #else
 #define F3_WPE_ATTR
 #endif
-template <int CELL, int LG, int NW, int DYN, int FPB1, int DBG, int FUSE>
+// SLOT (FPB1 only): the slot form of the window (file header) - D0 lanes are (ion, slot of its list), no flat task space.
+template <int CELL, int LG, int NW, int DYN, int FPB1, int DBG, int FUSE, int SLOT = 0>
 __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill3ArgsPtr full)
 {
+    static_assert(!SLOT || FPB1, "the slot form is for one frame per workgroup");
     constexpr int VP = 1 << LG;
     constexpr bool CHEAP = CELL == 1;                           // minimum-image distances, decisions on the logistic argument
     constexpr int NT = NW * 64;
@@ -696,7 +732,7 @@ __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill
     double etv = 0.0;
     if (tid < F3_EXPN) etv = h.exptab[tid];                    // in flight beside the frame loads; parked below
     for (int q = lane; q < TT; q += 64) ttab[q] = 0u;          // stale entries must stay valid tasks (landmark 0, ion 0)
-    for (int q = lane; q < (FPB1 ? 2 * (IW + 1) : 4 * IW + (IW + 4) / 4); q += 64) ionrec[q] = 0u;      // stale tasks look their ion up
+    if (!SLOT) for (int q = lane; q < (FPB1 ? 2 * (IW + 1) : 4 * IW + (IW + 4) / 4); q += 64) ionrec[q] = 0u;      // stale tasks look their ion up
     // ---- phase 1a: copy this workgroup's atoms into LDS ----
     {
         // (g.frame_mod > 0, an experiment: the workgroups read the first frame_mod frames over and over - the frames then
@@ -821,6 +857,9 @@ __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill
             const int b = bin_of3<CELL>(P, x, y, z, g.pG0, g.pG1, g.pG2);
             i32 lo, hi;                                              // one 8-byte load (two loads take the L1 twice)
             { uint2 pr; __builtin_memcpy(&pr, g.p_off + b, 8); lo = (i32)pr.x; hi = (i32)pr.y; }
+            // SLOT: a list longer than eight entries (few frames have one) widens the slots of the frame's windows; its
+            // length goes to the high word of fmax[] (the low word is the beyond-delta flag)
+            if (SLOT && hi - lo > 8) atomicMax((unsigned *)fmax + 2 * fl + 1, (unsigned)(hi - lo));
             unsigned fb = 0u;
             if (h.has_fallback) fb = (unsigned)bin_of3<CELL>(P, x, y, z, g.fG0, g.fG1, g.fG2);
             ioninfo[fl * M + (r - S)] = make_uint2((unsigned)lo, (unsigned)(hi - lo) | (fb << 8));
@@ -830,8 +869,19 @@ __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill
     __syncthreads();
     F3_STAMP(ts2);
     F3_SPAN(10, 1, ts1, ts2); F3_SPAN(12, 2, ts1, tsb); F3_SPAN(12, 3, tsb, ts2);
+    // SLOT: eight slots per ion, more in a frame that has a longer list (phase 1b left its length in fmax[]'s high word)
+    bool frame_tight = true;                                    // wave-uniform, as lgsl_frame
+    int lgsl_frame = 3;
+    if (SLOT) {
+        const uint2 fm = *(const uint2 *)fmax;
+        const unsigned beyond = (unsigned)__builtin_amdgcn_readfirstlane((int)fm.x), lmax = (unsigned)__builtin_amdgcn_readfirstlane((int)fm.y);
+        if (h.has_fallback) frame_tight = DYN ? (g.frame_dmax[f0] * g.frame_dmax[f0] <= g.delta2) : beyond == 0u;
+        lgsl_frame = 3 + (lmax > 8u) + (lmax > 16u) + (lmax > 32u) + (lmax > 64u);
+    }
     // fmax[fl] != 0: some static atom of frame fl moved beyond delta -> the frame takes the fallback table
-    if (tid < nf && h.has_fallback) {
+    if (SLOT) {
+        if (tid == 0 && !frame_tight) atomicAdd(&g.scal[2], 1ull);
+    } else if (tid < nf && h.has_fallback) {
         const bool tight = DYN ? (g.frame_dmax[f0 + tid] * g.frame_dmax[f0 + tid] <= g.delta2) : (fmax[tid] == 0ull);
         if (!tight) atomicAdd(&g.scal[2], 1ull);
     }
@@ -857,43 +907,64 @@ __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill
     bool spilled = false;                                       // wave-uniform
     for (int ib0 = wave * IW; ib0 < nions; ib0 += NW * IW) {
         const int nib = (nions - ib0) < IW ? (nions - ib0) : IW;
-        // ---- A: a lane per ion of the window: its list, the first task of the list (a prefix sum) ----
+        // ---- A: a lane per ion of the window ----
         int fl = 0, j = 0, nL = 0;
         unsigned lo = 0u;
-        if (lane < nib) {
-            const int ion = ib0 + lane;
-            if (!FPB1) for (int q = 1; q < nf; q++) fl += ion >= q * M;
-            j = ion - fl * M;
-            const uint2 ii = ioninfo[ion];
-            lo = ii.x; nL = (int)(ii.y & 255u);
-            if (h.has_fallback) {
-                const bool tight = DYN ? (g.frame_dmax[f0 + fl] * g.frame_dmax[f0 + fl] <= g.delta2) : (fmax[fl] == 0ull);
-                if (!tight) {
-                    const unsigned fb = ii.y >> 8;
+        int nlt = 0, lgsl = 0;                                  // candidate tasks of the window (flat form); log2 of the slots per ion
+        if (SLOT) {
+            // slot form: nothing to set up - a D0 lane finds its ion and its slot from its number and the ion's list in
+            // ioninfo[].  A frame that takes the fallback table (rare) has its ions' lists looked up here and written
+            // over their ioninfo[] (the ions of a window are this wave's alone), and picks its slot width itself.
+            lgsl = lgsl_frame;
+            if (lane < nib) { j = ib0 + lane; nzc[lane] = 0u; }
+            if (h.has_fallback && !frame_tight) {
+                if (lane < nib) {
+                    const unsigned fb = ioninfo[ib0 + lane].y >> 8;
                     uint2 pr;
                     __builtin_memcpy(&pr, g.f_off + fb, 8);
-                    nL = (int)(pr.y - pr.x); lo = g.f_base + pr.x;
+                    nL = (int)(pr.y - pr.x);
+                    ioninfo[ib0 + lane] = make_uint2(g.f_base + pr.x, (unsigned)nL | (fb << 8));
+                }
+                lgsl = 3 + (__ballot(nL > 8) != 0ull) + (__ballot(nL > 16) != 0ull) + (__ballot(nL > 32) != 0ull) + (__ballot(nL > 64) != 0ull);
+            }
+            if (lgsl > 6) { if (lane == 0) atomicAdd(&g.scal[3], 1ull); break; }      // cannot happen (the host takes the flat form then)
+        } else {
+            // flat form: the list of every ion, the first task of the list (a prefix sum)
+            if (lane < nib) {
+                const int ion = ib0 + lane;
+                if (!FPB1) for (int q = 1; q < nf; q++) fl += ion >= q * M;
+                j = ion - fl * M;
+                const uint2 ii = ioninfo[ion];
+                lo = ii.x; nL = (int)(ii.y & 255u);
+                if (h.has_fallback) {
+                    const bool tight = DYN ? (g.frame_dmax[f0 + fl] * g.frame_dmax[f0 + fl] <= g.delta2) : (fmax[fl] == 0ull);
+                    if (!tight) {
+                        const unsigned fb = ii.y >> 8;
+                        uint2 pr;
+                        __builtin_memcpy(&pr, g.f_off + fb, 8);
+                        nL = (int)(pr.y - pr.x); lo = g.f_base + pr.x;
+                    }
                 }
             }
-        }
-        const int inL = wave_add_scan(nL), exL = inL - nL;
-        const int nlt = __builtin_amdgcn_readlane(inL, 63);     // candidate tasks of the window
-        if (nlt > h.mcap) { if (lane == 0) atomicAdd(&g.scal[3], 1ull); break; }      // cannot happen (host sizes mcap)
-        // the ion of a candidate task (round 5): a bit on the LAST task of every non-empty list; a task's list is then the
-        // r-th non-empty one, r = the number of bits below the task - two mbcnt on a scalar mask per pass, where a byte
-        // marker per task took a maximum scan over the lanes (6 DPP steps + 6 max)
-        for (int q = lane; q < 2 * ((nlt + 63) >> 6); q += 64) mark[q] = 0u;
-        {
-            const unsigned long long nem = __ballot(nL > 0);
-            if (lane < nib) {
-                if (nL > 0) {
-                    const int rk = mask_rank(nem, 0);
-                    atomicOr(&mark[(inL - 1) >> 5], 1u << ((inL - 1) & 31));
-                    if (FPB1) ((uint2 *)ionrec)[rk] = make_uint2(lo - (unsigned)exL, (unsigned)lane);
-                    else rk2ion[rk] = (unsigned char)lane;
+            const int inL = wave_add_scan(nL), exL = inL - nL;
+            nlt = __builtin_amdgcn_readlane(inL, 63);           // candidate tasks of the window
+            if (nlt > h.mcap) { if (lane == 0) atomicAdd(&g.scal[3], 1ull); break; }      // cannot happen (host sizes mcap)
+            // the ion of a candidate task (round 5): a bit on the LAST task of every non-empty list; a task's list is then the
+            // r-th non-empty one, r = the number of bits below the task - two mbcnt on a scalar mask per pass, where a byte
+            // marker per task took a maximum scan over the lanes (6 DPP steps + 6 max)
+            for (int q = lane; q < 2 * ((nlt + 63) >> 6); q += 64) mark[q] = 0u;
+            {
+                const unsigned long long nem = __ballot(nL > 0);
+                if (lane < nib) {
+                    if (nL > 0) {
+                        const int rk = mask_rank(nem, 0);
+                        atomicOr(&mark[(inL - 1) >> 5], 1u << ((inL - 1) & 31));
+                        if (FPB1) ((uint2 *)ionrec)[rk] = make_uint2(lo - (unsigned)exL, (unsigned)lane);
+                        else rk2ion[rk] = (unsigned char)lane;
+                    }
+                    if (!FPB1) ((uint4 *)ionrec)[lane] = make_uint4(lo - (unsigned)exL, 24u * (unsigned)(fl * SM + S + j), 24u * (unsigned)(fl * SM), (unsigned)fl);
+                    nzc[lane] = 0u;
                 }
-                if (!FPB1) ((uint4 *)ionrec)[lane] = make_uint4(lo - (unsigned)exL, 24u * (unsigned)(fl * SM + S + j), 24u * (unsigned)(fl * SM), (unsigned)fl);
-                nzc[lane] = 0u;
             }
         }
         if (DBG && dbg == 9 && lane == 0) { atomicAdd(&g.scal[5], (u64)nlt); atomicAdd(&g.scal[7], 1ull); }
@@ -903,16 +974,20 @@ __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill
         int t_end = 0, carry = 0, cnt = 0;
         spilled = false;
         const int nlt0 = (DBG && dbg == 2) ? 0 : nlt;           // ablation: stop after the owner stage
-        for (int base = 0; base < nlt0; base += 64) {
-            // ---- D0: a lane per candidate task (F3_D0_PASSES) ----
+        // D0 runs over the window's tasks 64 a pass, or (SLOT) over its ions 64 >> lgsl a pass, 1 << lgsl slots each
+        const int d0_lim = SLOT ? ((DBG && dbg == 2) ? 0 : nib) : nlt0, d0_step = SLOT ? 64 >> lgsl : 64;
+        const int s_ion = lane >> lgsl, s_slot = lane & ((1 << lgsl) - 1);
+        const unsigned s_ioff = 24u * (unsigned)s_ion;
+        for (int base = 0; base < d0_lim; base += d0_step) {
+            // ---- D0: a lane per candidate task, or per (ion, slot) (F3_D0_PASSES) ----
             F3_STAMP(ts4);
             // (round 5: two passes at a time where two are left and the table has room for both - their list entries are
             // then on their way together, one L2 round trip instead of two; not in the sixteen-wave build, which has no
             // registers to spare)
-            if (NW < 16 && base + 64 < nlt0 && t_end <= TT - 128) { F3_D0_PASSES(2); base += 64; }
+            if (NW < 16 && base + d0_step < d0_lim && t_end <= TT - 128) { F3_D0_PASSES(2); base += d0_step; }
             else F3_D0_PASSES(1);
             if (DBG == 2 && dbg >= 10) { unsigned long long tq = __builtin_amdgcn_s_memtime(); acc_d0 += tq - ts4; ts4 = tq; }
-            if (t_end <= TT - 64 && base + 64 < nlt0) continue;         // room for another pass of candidates
+            if (t_end <= TT - 64 && base + d0_step < d0_lim) continue;  // room for another pass of candidates
             if (DBG && dbg == 9 && lane == 0) atomicAdd(&g.scal[4], (u64)t_end);
             if (DBG && dbg == 3) t_end = 0;                     // ablation: stop after the critical-vertex test
             // ---- the task table is drained: passes of TPP tasks over [0, t_end) ----
@@ -1163,6 +1238,7 @@ static int fill3_pack_lists(sit_ctx *c, bool have_tight, bool cheap)
     int rc;
     if ((rc = dev_alloc(c, &c->d_pack, 4 * ((i64)nt + (i64)nl + 1)))) return rc;       // 16 bytes per entry
     uint4 *pk = (uint4 *)c->d_pack;
+    HIP_TRY(c, hipMemsetAsync(pk + (nt + nl), 0, 16, c->stream));      // the spare entry: idle lanes of the slot form read entry 0, even of an empty array
     const int lg = f3_vp(c) == 16 ? 4 : (f3_vp(c) == 8 ? 3 : 2), rsh = cheap ? 4 : 5;      // (k_fill3: KSH = lg + rsh)
     if (nt > 0) k_pack_lists<<<dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, c->stream>>>(c->d_tbin_list, c->d_tbin_crit, nt, lg, rsh, (const uint4 *)c->d_vh, pk, cheap ? 1 : 0);
     if (nl > 0) k_pack_lists<<<dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, c->stream>>>(c->d_bin_list, c->d_bin_crit, nl, lg, rsh, (const uint4 *)c->d_vh, pk + nt, cheap ? 1 : 0);
@@ -1183,7 +1259,7 @@ bool fill3_eligible(sit_ctx *c)
 
 // the instantiation for this cell / landmark width / waves per workgroup / mapping mode / frames per workgroup
 static hipError_t f3_dispatch(sit_ctx *c, const Fill3Head &h_in, Fill3ArgsPtr full, unsigned grid, size_t lds, int nw, int vp,
-                              bool diag, bool dynmap, bool fuse)
+                              bool diag, bool dynmap, bool fuse, bool slot)
 {
     Fill3Head h = h_in;
     {
@@ -1192,19 +1268,20 @@ static hipError_t f3_dispatch(sit_ctx *c, const Fill3Head &h_in, Fill3ArgsPtr fu
         const int v[12] = {L.fmax, L.gsync, L.ioninfo, L.etab, L.wave0, L.o_ionrec, L.o_ttab, L.o_sv, L.o_nzc, L.o_mark, L.wbytes, L.total};
         for (int i = 0; i < 12; i++) h.lay[i] = v[i];
     }
-#define F3_LAUNCH(CELL, LGV, NWV, DY, F1, DB, FU)                                                                              \
+#define F3_LAUNCH(CELL, LGV, NWV, DY, F1, DB, FU, SL)                                                                          \
     do {                                                                                                                   \
-        hipError_t e = lds_limit((const void *)k_fill3<CELL, LGV, NWV, DY, F1, DB, FU>, lds, c->device);                   \
+        hipError_t e = lds_limit((const void *)k_fill3<CELL, LGV, NWV, DY, F1, DB, FU, SL>, lds, c->device);               \
         if (e != hipSuccess) return e;                                                                                     \
-        k_fill3<CELL, LGV, NWV, DY, F1, DB, FU><<<dim3(grid), dim3(NWV * 64), lds, c->stream>>>(h, full);                  \
+        k_fill3<CELL, LGV, NWV, DY, F1, DB, FU, SL><<<dim3(grid), dim3(NWV * 64), lds, c->stream>>>(h, full);              \
     } while (0)
+    // (the slot form exists for the plain, the fused and the phase-clock build: fill3_slot_ok)
 #define F3_PICK3(CELL, LGV, NWV, F1)                                                                                           \
     do {                                                                                                                   \
-        if (dynmap) F3_LAUNCH(CELL, LGV, NWV, 1, F1, 0, 0);                                                                \
-        else if (h.debug_stop >= 10) F3_LAUNCH(CELL, LGV, NWV, 0, F1, 2, 0);                                                  \
-        else if (h.debug_stop) F3_LAUNCH(CELL, LGV, NWV, 0, F1, 1, 0);                                                     \
-        else if (fuse) F3_LAUNCH(CELL, LGV, NWV, 0, F1, 0, 1);                                                             \
-        else F3_LAUNCH(CELL, LGV, NWV, 0, F1, 0, 0);                                                                       \
+        if (dynmap) F3_LAUNCH(CELL, LGV, NWV, 1, F1, 0, 0, 0);                                                             \
+        else if (h.debug_stop >= 10) { if (F1 && slot) F3_LAUNCH(CELL, LGV, NWV, 0, F1, 2, 0, F1); else F3_LAUNCH(CELL, LGV, NWV, 0, F1, 2, 0, 0); } \
+        else if (h.debug_stop) F3_LAUNCH(CELL, LGV, NWV, 0, F1, 1, 0, 0);                                                  \
+        else if (fuse) { if (F1 && slot) F3_LAUNCH(CELL, LGV, NWV, 0, F1, 0, 1, F1); else F3_LAUNCH(CELL, LGV, NWV, 0, F1, 0, 1, 0); } \
+        else { if (F1 && slot) F3_LAUNCH(CELL, LGV, NWV, 0, F1, 0, 0, F1); else F3_LAUNCH(CELL, LGV, NWV, 0, F1, 0, 0, 0); } \
     } while (0)
 #define F3_PICK(CELL, LGV)                                                                                                     \
     do {                                                                                                                   \
@@ -1396,6 +1473,22 @@ int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64
     iw = iw_for(nw, fpb);
     SIT_REQUIRE(c, (i64)iw * wmax <= 65536, "sit_fill: candidate lists too long for the third-generation kernel");
     h.fpb = fpb; h.iw = iw; h.mcap = mcap_for(iw);
+    // The slot form of the window (SLOT): possible with one frame per workgroup, lists of at most 64 entries in every table
+    // the launch can meet, no dynamic mapping and no ablation stop (the phase clocks have it).  Taken by default where it
+    // measured faster: four-wave workgroups whose primary table has no list longer than eight entries - every frame that
+    // stays on that table then runs eight slots per ion (C2: windows of 16 ions, two D0 passes in either form).
+    // SITATOR_F3_SLOT = 0 / 1 overrides the default where the form is possible.
+    bool slot = false;
+    {
+        const int dstop = p->dynamic_lattice_mapping ? 0 : f3_env_int("SITATOR_DEBUG_STOP", 0);
+        const bool possible = (nw != 4 || fpb == 1) && wmax <= 64 && !p->dynamic_lattice_mapping && (dstop == 0 || dstop >= 10);
+        const i64 wprim = have_tight ? c->W_tight : c->W;
+        const int asked = f3_env_int("SITATOR_F3_SLOT", -1);
+        slot = possible && (asked < 0 ? (nw == 4 && wprim <= 8) : asked != 0);
+        int width = 8;
+        while (width < wmax) width *= 2;
+        c->last_slot = slot ? width : 0;                        // the widest slots a window of this launch can take
+    }
     // the fused assignment sits behind the window loop (and groups the windows of 64 / iw waves): one window per wave
     if (fuse && (i64)fpb * M > (i64)nw * iw) fuse = false;
     if (!fuse) store = true;                                    // the assignment kernels (if any) read the row buffers
@@ -1483,7 +1576,7 @@ int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64
                 float tq = 1e30f;
                 for (int rep = 0; rep < 5; rep++) {                            // the first launch of a shape warms it up; best of four
                     HIP_TRY(c, hipEventRecord(e0, c->stream));
-                    HIP_TRY(c, f3_dispatch(c, ht, full_t, gt, ldq, nw, vp, diag, dynmap, false));
+                    HIP_TRY(c, f3_dispatch(c, ht, full_t, gt, ldq, nw, vp, diag, dynmap, false, slot));
                     HIP_TRY(c, hipEventRecord(e1, c->stream));
                     HIP_TRY(c, hipEventSynchronize(e1));
                     float ms = 0;
@@ -1513,7 +1606,7 @@ int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64
         c->fuse_wlist = a.wlist; c->fuse_wcount = a.wcount; c->fuse_seg_cap = seg_cap; c->fuse_nseg = nseg;
     } else if (fuse_asked && (rc = reset_fill_words(c))) return rc;   // a caller that asks for the fused pass leaves the reset to it
     if (f_hi <= f_lo) return SIT_OK;
-    HIP_TRY(c, f3_dispatch(c, h, full, grid, lds, nw, vp, diag, dynmap, fuse));
+    HIP_TRY(c, f3_dispatch(c, h, full, grid, lds, nw, vp, diag, dynmap, fuse, slot));
     if (h.debug_stop >= 10) { k_f3_spans<<<dim3(1), dim3(64), 0, c->stream>>>(a.dbgbuf, c->d_scal); HIP_TRY(c, hipGetLastError()); }
     return SIT_OK;
 }

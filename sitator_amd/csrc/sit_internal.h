@@ -85,6 +85,7 @@ struct sit_ctx {
     bool f3_ref_in_cell = false;      // every reference position within [-0.25, 1.25) of the cell (k_fill3 may leave statics unwrapped)
     bool f3_cheap_ok = false;         // k_fill3 may decide on the logistic argument (diagonal cell, steepness > 0, vcd > 0)
     double f3_x0lo = 0, f3_x0hi = 0;  // the argument at the cut-off -/+ the error bound of the kernel's
+    int last_slot = 0;                // k_fill3's slot form in the last sit_fill: the widest slots per ion a window could take (0: the flat task space)
     bool last_fused = false;          // the last sit_fill assigned the narrow rows inside the fill kernel
     i32 *fuse_wlist = nullptr;        // ... and listed the others here (segments of the scratch buffer)
     unsigned *fuse_wcount = nullptr;
