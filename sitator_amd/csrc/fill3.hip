@@ -185,6 +185,13 @@ struct ExpK {
     double log2e_128, magic, ln2_128, c4, c3, smid;
 };
 __device__ __forceinline__ double in_vgpr(double x) { asm volatile("" : "+v"(x)); return x; }
+// max(x, c) for x that is never a NaN, as ONE instruction (__builtin_fmax puts a canonicalising v_max_f64 x, x, x in front)
+__device__ __forceinline__ double max_f64(double x, double c)
+{
+    double r;
+    asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(x), "s"(c));
+    return r;
+}
 __device__ __forceinline__ ExpK expk_make(double mid, double steep)
 {
     ExpK k;
@@ -201,7 +208,7 @@ __device__ __forceinline__ ExpK expk_make(double mid, double steep)
 // term is r^5 / 120 < 1.3e-15)
 __device__ __forceinline__ double exp_tab(double x, const double *tab, const ExpK &k)
 {
-    x = __builtin_fmax(x, -700.0);                     // exp(-700) ~ 1e-304: 1 + e == 1 all the same, no denormals
+    x = max_f64(x, -700.0);                            // exp(-700) ~ 1e-304: 1 + e == 1 all the same, no denormals
     double u;                                          // (left to itself the compiler copies magic and uses v_fmac)
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(u) : "v"(x), "v"(k.log2e_128), "v"(k.magic));
     const double n = u - k.magic;
@@ -254,6 +261,15 @@ __device__ __forceinline__ double root_chain(double p, int nv)
     if (nv == 2) return rsqrt_nr(p);
     if (nv == 1) return rcp_nr(p);
     return pow_generic3(p, nv);
+}
+
+// 24 a + b for a < 2^24 as ONE full-rate instruction (the compiler folds b into the product's operand and takes the
+// quarter-rate v_mul_lo_u32, also where it is given the 24-bit multiply)
+__device__ __forceinline__ unsigned mad24_24(unsigned a, unsigned b)      // b: wave-uniform
+{
+    unsigned r;
+    asm("v_mad_u32_u24 %0, %1, 24, %2" : "=v"(r) : "v"(a), "s"(b));
+    return r;
 }
 
 // ---- wave helpers --------------------------------------------------------------------------------------------------
@@ -341,7 +357,7 @@ __device__ __forceinline__ int bin_of3(const Pbc &P, double px, double py, doubl
         VOFF = (R0X); STATOFF = 0u; FLX = 0u;                                                                              \
         const unsigned ion_ = (TK) & ~KMASK;                                                                               \
         if (FPB1) {                                                                                                        \
-            IONOFF = ionbase + 24u * ion_;                                                                                 \
+            IONOFF = mad24_24(ion_, ionbase);                                                                              \
             if (DYN) VOFF = 24u * (unsigned)g.lattice_map[f0 * S + (i64)(R0Y)];                                            \
         } else {                                                                                                           \
             const uint4 ir = ((const uint4 *)ionrec)[ion_];                                                                \
@@ -442,20 +458,39 @@ __device__ __forceinline__ int bin_of3(const Pbc &P, double px, double py, doubl
 // sends the passes round again with EX = 1: the reference's own squared distance (util/PBCCalculator.pyx:64-103; the
 // ion's slot holds -ion, the offset is centroid - ion as in helpers.pyx:100) against the exact threshold.  The zero
 // pattern stays the reference's bit for bit.
+// F3_D1E_LOAD: the task words of NP passes from pass C0 on, then their vertex records - all of them requested before the
+// first is used.  The empty asm statement orders the issue (as in F3_D0_PASSES) and differs between NP = 1 and NP = 2:
+// left alone the compiler merged the equal heads of the one- and the two-pass body and decided "one pass or two" behind
+// the wait for the first pass's record - every pass a round trip of its own.  CLAMP: a request ahead may reach past the
+// table's last task; the stale entries it then reads are valid tasks (ttab is cleared at the start), but the index must
+// stay inside the table.
+#define F3_D1E_LOAD(NP, C0, TK, R0, CLAMP)                                                                                 \
+    do {                                                                                                                   \
+        _Pragma("unroll") for (int u = 0; u < NP; u++) {                                                                   \
+            int tb_ = TPP * ((C0) + u);                                                                                    \
+            if (CLAMP) tb_ = tb_ < TT - TPP ? tb_ : TT - TPP;        /* (scalar unit) */                                   \
+            TK[u] = ttab[tb_ + gi];                                                                                        \
+        }                                                                                                                  \
+        if (NP == 2) asm volatile("" : "+v"(TK[0]), "+v"(TK[NP - 1])); else asm volatile("" : "+v"(TK[0]));                \
+        _Pragma("unroll") for (int u = 0; u < NP; u++)               /* offset, static id, steepness / vcd: ONE gather */  \
+            R0[u] = *(const uint4 *)(vh + ((TK[u] & KMASK) | hh32));                                                       \
+    } while (0)
 #define F3_D1E_BODY(NP, EX, REDO)                                                                                          \
     do {                                                                                                                   \
         constexpr bool APPROX = CHEAP && !(EX);                                                                            \
         double d2_[NP], rv_[NP], f_[NP];                                                                                   \
-        unsigned tk_[NP];                                                                                                  \
         unsigned long long bad_[NP];                                                                                       \
+        uint2 r1_[NP];                                               /* the exact thresholds (32-byte records): for the */ \
+        _Pragma("unroll") for (int u = 0; u < NP; u++) {             /* redo pass of a diagonal cell, all passes' at once */ \
+            r1_[u] = make_uint2(0u, 0u);                                                                                   \
+            if (CHEAP && (EX)) r1_[u] = *(const uint2 *)((const char *)g.vh + 2u * ((tk_[u] & KMASK) | hh32) + 16);        \
+        }                                                                                                                  \
         _Pragma("unroll") for (int u = 0; u < NP; u++) {                                                                   \
             const int tb = TPP * (cursor + u);                                                                             \
-            tk_[u] = ttab[tb + gi];                                                                                        \
-            const char *rp = vh + ((tk_[u] & KMASK) | hh32);                                                               \
-            const uint4 r0 = *(const uint4 *)rp;                     /* offset, static id, steepness / vcd: ONE gather */  \
-            uint2 r1 = make_uint2(0u, 0u);                                                                                 \
-            if (!APPROX) r1 = CHEAP ? *(const uint2 *)((const char *)g.vh + 2u * ((tk_[u] & KMASK) | hh32) + 16)           \
-                                    : *(const uint2 *)(rp + 16);     /* the exact threshold (32-byte records) */             \
+            uint4 r0 = r0_[u];                                                                                             \
+            if (!PF) asm volatile("" : "+v"(r0.y));                  /* (keeps the record one 16-byte load) */             \
+            uint2 r1 = r1_[u];                                                                                             \
+            if (!CHEAP) r1 = *(const uint2 *)(vh + ((tk_[u] & KMASK) | hh32) + 16);   /* (general cells: where it is used) */ \
             unsigned voff, ionoff, statoff, flx_;                                                                          \
             F3_TASK_OFFSETS(tk_[u], r0.x, r0.y, voff, ionoff, statoff, flx_);                                              \
             rv_[u] = __hiloint2double((int)r0.w, (int)r0.z);                                                               \
@@ -521,6 +556,12 @@ __device__ __forceinline__ int bin_of3(const Pbc &P, double px, double py, doubl
     } while (0)
 #define F3_D1E_PASSES(NP)                                                                                                  \
     do {                                                                                                                   \
+        unsigned tk_[NP];                                                                                                  \
+        uint4 r0_[NP];                                                                                                     \
+        if (PF) {                                                                                                          \
+            _Pragma("unroll") for (int u = 0; u < NP; u++) { tk_[u] = tkn_[u]; r0_[u] = rn_[u]; }                          \
+            if (NP == 2 && cursor + 2 < pend) F3_D1E_LOAD(2, cursor + 2, tkn_, rn_, true);                                 \
+        } else F3_D1E_LOAD(NP, cursor, tk_, r0_, false);                                                                   \
         bool redo_ = false;                                          /* wave-uniform */                                    \
         F3_D1E_BODY(NP, 0, redo_);                                                                                         \
         if (CHEAP && redo_) {                                                                                              \
@@ -528,6 +569,8 @@ __device__ __forceinline__ int bin_of3(const Pbc &P, double px, double py, doubl
             bool never_ = false;                                                                                           \
             F3_D1E_BODY(NP, 1, never_);                                                                                    \
         }                                                                                                                  \
+        /* (a single pass that is not the table's last: the list is nearly full - rare; its successors are fetched anew) */ \
+        if (PF && NP == 1 && cursor + 1 < pend) F3_D1E_LOAD(2, cursor + 1, tkn_, rn_, true);                               \
     } while (0)
 
 // T: the n-th root (helpers.pyx:212) of the product (:208), one lane per survivor of the wave's list; the row entry of a
@@ -901,6 +944,12 @@ __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill
     // FUSE: the windows of GW waves (64 ions or fewer) are assigned together, by the last of them to finish; a wave has
     // ONE window (the host makes sure: fpb M <= NW IW, else the assignment stays a kernel of its own).
     const int GW = FUSE ? (IW <= 32 ? 64 / IW : 1) : 1;
+    // D1 + E (F3_D1E_PASSES): the task words and vertex records of the NEXT two passes are requested ahead of the arithmetic
+    // of the current two - where the instantiation has the registers for it: not the sixteen-wave builds (three to spare
+    // below eight waves per SIMD), nor several frames per workgroup or the debug builds (they would spill)
+    constexpr bool PF = NW < 16 && FPB1 && !DBG;
+    unsigned tkn_[2] = {0u, 0u};
+    uint4 rn_[2] = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u)};
 
     // ---- phase 2: every wave on its own (windows of IW ions); no workgroup barrier from here on ----
     const int nions = nf * M;
@@ -993,12 +1042,14 @@ __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill
             // ---- the task table is drained: passes of TPP tasks over [0, t_end) ----
             const int pend = (t_end + TPP - 1) / TPP;
             int cursor = 0;
+            if (PF && pend > 0) F3_D1E_LOAD(2, 0, tkn_, rn_, false);
             while (cursor < pend) {
                 // ---- D1 + E: one squared distance per (task, vertex) lane (helpers.pyx:174-178 before the sqrt),
                 //      compared with the exact threshold, and the logistic factor of the vertex (helpers.pyx:196-205);
                 //      the factors of a task are multiplied across its lanes and the tasks with every vertex inside
                 //      are appended to the survivors.  Two passes per iteration (loads and arithmetic of both
-                //      interleaved) while the list has room for every task of both ----
+                //      interleaved; PF: the records were requested an iteration ahead) while the list has room for
+                //      every task of both ----
                 while (cursor < pend && cnt + TPP <= rcap) {
                     if (cursor + 1 < pend && cnt + 2 * TPP <= rcap) {
                         F3_D1E_PASSES(2);
@@ -1055,6 +1106,7 @@ __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill
 }
 #undef F3_ASSIGN
 #undef F3_D1E_BODY
+#undef F3_D1E_LOAD
 #undef F3_TASK_OFFSETS
 
 // ---- host side ------------------------------------------------------------------------------------------------------
