@@ -431,6 +431,9 @@ __global__ __launch_bounds__(256) void k_max_nnz(const i32 *nnz, i64 n, i32 *out
     if ((threadIdx.x & 63) == 0 && m > 0) { atomicMax(out, m); atomicAdd(out + 1, t); }
 }
 
+// the leading frames the row width is measured on: 2^16 rows, at least 16 frames, never past the F frames at hand
+static i64 leading_frames(i64 M, i64 F) { return std::min(std::max<i64>((1 << 16) / M, 16), F); }
+
 static int measured_row_width(sit_ctx *c, const sit_fill_params *p, i64 *W_out)
 {
     *W_out = c->W;
@@ -442,9 +445,7 @@ static int measured_row_width(sit_ctx *c, const sit_fill_params *p, i64 *W_out)
         return SIT_OK;
     }
     if ((mode && mode[0] == 'l') || c->rows_overflowed || c->W <= 4 || c->F == 0 || p->dynamic_lattice_mapping || !fill3_eligible(c)) return SIT_OK;
-    i64 Fs = (1 << 16) / c->M;
-    Fs = Fs < 16 ? 16 : Fs;
-    if (Fs > c->F) Fs = c->F;
+    const i64 Fs = leading_frames(c->M, c->F);
     const i64 Ns = Fs * c->M, W = c->W;
     int rc = ensure_scratch(c, Ns * (4 + 12 * W) + 64);
     if (rc) return rc;
@@ -512,20 +513,27 @@ void fill_ring_free(sit_ctx *c)
     c->fill_ring = nullptr;
 }
 
+// The words every fill leaves behind - hb[0] the error key, hb[1..4] all-zero rows, exact redos, frames on the fallback
+// table, "a row outgrew its buffer" - into the context and the caller's variables; returns the error's kind
+static int decode_fill_words(sit_ctx *c, const u64 *hb, i64 *n_all_zero, sit_error *err, bool *overflow)
+{
+    if (n_all_zero) *n_all_zero = (i64)hb[1];
+    c->fallback_frames = (i64)hb[3];
+    c->band_redos = (i64)hb[2];
+    *overflow = hb[4] != 0;
+    return decode_error(c, hb[0], err);
+}
+
 // decode one landed result; returns its status
 // (superseded: a pass at the rigorous row width has been enqueued behind this one - its overflow has been served already and
 // the flags belong to the later pass)
 static int fill_decode(sit_ctx *c, const FillPending &s, i64 *n_all_zero, sit_error *err, bool superseded)
 {
-    const u64 *hb = s.host;
-    const u64 hkey = hb[0], hs[4] = {hb[1], hb[2], hb[3], hb[4]};
-    for (int q = 0; q < 4; q++) c->census[q] = (double)hb[5 + q];
-    if (n_all_zero) *n_all_zero = (i64)hs[0];
-    c->fallback_frames = (i64)hs[2];
-    c->band_redos = (i64)hs[1];
-    const int kind = decode_error(c, hkey, err);
+    for (int q = 0; q < 4; q++) c->census[q] = (double)s.host[5 + q];
+    bool overflow;
+    const int kind = decode_fill_words(c, s.host, n_all_zero, err, &overflow);
     if (kind != SIT_OK) { c->assign_valid = false; return kind; }
-    if (s.v3 && hs[3]) {
+    if (s.v3 && overflow) {
         if (s.rows_measured && superseded) return SIT_OK;
         c->assign_valid = false; c->rows_valid = false;
         if (s.rows_measured) { c->rows_overflowed = true; return SIT_RETRY; }       // a row beyond the measured width: once more at the rigorous one
@@ -603,6 +611,22 @@ extern "C" int sit_fill_result(sit_ctx *c, i64 *n_all_zero, sit_error *err)
     return rc;
 }
 
+// row buffers of N rows of W slots (sit_fill and the pipelined call)
+static int ensure_row_buffers(sit_ctx *c, i64 N, i64 W)
+{
+    if (c->rows_W == W && c->rows_N == N && c->d_row_nnz) return SIT_OK;
+    c->rows_valid = false;
+    int rc;
+    if ((rc = dev_alloc(c, &c->d_row_nnz, N))) return rc;
+    if ((rc = dev_alloc(c, &c->d_row_idx, N * W))) return rc;
+    if ((rc = dev_alloc(c, &c->d_row_val, N * W))) return rc;
+    // slots beyond a row's nnz are never written by the fill kernels: give them a defined content once
+    HIP_TRY(c, hipMemsetAsync(c->d_row_idx, 0, (size_t)(N * W > 0 ? N * W : 1) * 4, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_row_val, 0, (size_t)(N * W > 0 ? N * W : 1) * 8, c->stream));
+    c->rows_W = W; c->rows_N = N;
+    return SIT_OK;
+}
+
 extern "C" int sit_fill(sit_ctx *c, const sit_fill_params *p, i64 *n_all_zero, sit_error *err)
 {
     if (!c || !p) return SIT_ERR_INVALID;
@@ -648,16 +672,7 @@ extern "C" int sit_fill(sit_ctx *c, const sit_fill_params *p, i64 *n_all_zero, s
     for (int attempt = 0; attempt < 2; attempt++) {
         if (v3 && !(have_W && attempt == 0) && (rc = measured_row_width(c, p, &W))) return rc;
         const bool rows_measured = W < c->W;
-        if (c->rows_W != W || c->rows_N != N || !c->d_row_nnz) {
-            c->rows_valid = false;
-            if ((rc = dev_alloc(c, &c->d_row_nnz, N))) return rc;
-            if ((rc = dev_alloc(c, &c->d_row_idx, N * W))) return rc;
-            if ((rc = dev_alloc(c, &c->d_row_val, N * W))) return rc;
-            // slots beyond a row's nnz are never written by the fill kernels: give them a defined content once
-            HIP_TRY(c, hipMemsetAsync(c->d_row_idx, 0, (size_t)(N * W > 0 ? N * W : 1) * 4, c->stream));
-            HIP_TRY(c, hipMemsetAsync(c->d_row_val, 0, (size_t)(N * W > 0 ? N * W : 1) * 8, c->stream));
-            c->rows_W = W; c->rows_N = N;
-        }
+        if ((rc = ensure_row_buffers(c, N, W))) return rc;
         if (assign && (!c->d_labels || c->assign_N != N)) {
             if ((rc = dev_alloc(c, &c->d_labels, N))) return rc;
             if ((rc = dev_alloc(c, &c->d_confs, N))) return rc;
@@ -878,23 +893,13 @@ extern "C" int sit_upload_fill_fit(sit_ctx *c, const double *frames, i64 F, i64 
     i64 F_head = 0;                                           // leading frames already on the device
     if (!(c->d_row_nnz && c->rows_N == N && c->rows_W > 0 && c->rows_W <= c->W) && !c->rows_overflowed) {
         // the row width is measured on the leading frames (measured_row_width): they go up ahead of the pipeline
-        i64 Fs = (1 << 16) / M;
-        Fs = Fs < 16 ? 16 : Fs;
-        if (Fs > F) Fs = F;                                   // (as measured_row_width: never past the caller's frames)
+        const i64 Fs = leading_frames(M, F);
         HIP_TRY(c, hipMemcpyAsync(c->d_frames, frames, (size_t)(Fs * A * 24), hipMemcpyHostToDevice, c->stream));
         F_head = Fs;
         if ((rc = fill3_prepare(c))) return rc;
         if ((rc = measured_row_width(c, p, &W))) return rc;
     } else if (c->d_row_nnz && c->rows_N == N && c->rows_W > 0 && c->rows_W <= c->W && !c->rows_overflowed) W = c->rows_W;
-    if (c->rows_W != W || c->rows_N != N || !c->d_row_nnz) {
-        c->rows_valid = false;
-        if ((rc = dev_alloc(c, &c->d_row_nnz, N))) return rc;
-        if ((rc = dev_alloc(c, &c->d_row_idx, N * W))) return rc;
-        if ((rc = dev_alloc(c, &c->d_row_val, N * W))) return rc;
-        if (hipMemsetAsync(c->d_row_idx, 0, (size_t)(N * W) * 4, c->stream) != hipSuccess ||
-            hipMemsetAsync(c->d_row_val, 0, (size_t)(N * W) * 8, c->stream) != hipSuccess) { c->msg = "row buffers"; return SIT_ERR_HIP; }
-        c->rows_W = W; c->rows_N = N;
-    }
+    if ((rc = ensure_row_buffers(c, N, W))) return rc;
     if (hipMemsetAsync(c->d_err, 0xFF, sizeof(u64), c->stream) != hipSuccess ||
         hipMemsetAsync(c->d_scal, 0, sizeof(u64) * 16, c->stream) != hipSuccess) { c->msg = "counters"; return SIT_ERR_HIP; }
     if (dbgpipe) { (void)hipStreamSynchronize(c->stream); fprintf(stderr, "  row buffers at %.1f ms\n", since()); }
@@ -992,13 +997,10 @@ extern "C" int sit_upload_fill_fit(sit_ctx *c, const double *frames, i64 F, i64 
         return finish(SIT_ERR_HIP);
     }
     finish(SIT_OK);
-    const u64 hkey = hb[0], hs[4] = {hb[1], hb[2], hb[3], hb[4]};
-    if (n_all_zero) *n_all_zero = (i64)hs[0];
-    c->fallback_frames = (i64)hs[2];
-    c->band_redos = (i64)hs[1];
-    const int kind = decode_error(c, hkey, err);
+    bool overflow;
+    const int kind = decode_fill_words(c, hb, n_all_zero, err, &overflow);     // (no census, no assignment: not touched here)
     if (kind != SIT_OK) return kind;
-    if (hs[3]) {
+    if (overflow) {
         if (c->rows_W < c->W) {
             // a row beyond the measured width: the separate calls at the rigorous width (the fit starts again with them)
             c->rows_overflowed = true; c->rows_valid = false;

@@ -55,8 +55,7 @@
 #include <cstring>
 
 #include "sit_internal.h"
-
-#define F3_EXPN 128
+#include "fill3_plan.h"              // F3_EXPN, F3Layout / f3_layout, the launch plan
 
 // read with scalar loads from a device copy (the kernel is short of scalar registers: arguments parked there are
 // loaded where they are used)
@@ -121,40 +120,6 @@ struct Fill3Head {
     double safe2;                     // (the other thresholds of the static check are met on its rare path only: Fill3Args)
 };
 typedef const Fill3Args __attribute__((address_space(4))) *Fill3ArgsPtr;
-
-// LDS of a workgroup, in bytes from the start of the dynamic allocation
-struct F3Layout {
-    int fmax, gsync, ioninfo, etab, wave0;               // after xyz[fpb][S + M][3] at offset 0
-    int o_ionrec, o_ttab, o_sv, o_nzc, o_mark, wbytes;   // inside a wave's region (prod at its offset 0)
-    int total;
-};
-// rcap survivor slots (multiple of 8, <= 64), windows of iw ions (multiple of 4, <= 64), a task table of tt entries
-// (multiple of 64), mcap marker bytes (multiple of 64, >= the candidates of a window)
-__host__ __device__ inline F3Layout f3_layout(int fpb, int SM, int M, int nw, int rcap, int iw, int tt, int mcap, int fpb1)
-{
-    F3Layout L;
-    int o = fpb * SM * 24;
-    o = (o + 15) & ~15;                                  // LDS-DMA lands whole 16-byte pieces
-    L.fmax = o; o += fpb * 8 + ((fpb * (SM - M) + 63) / 64) * 8;      // + a bit per static atom: LDS holds its WRAPPED position (skipw)
-    L.gsync = o; o += nw * 8;                            // FUSE: arrivals per group of waves, "window spilled" per wave
-    L.ioninfo = o; o += fpb * M * 8;                     // {first entry, entries | fallback bin << 8} per ion
-    L.etab = o; o += F3_EXPN * 8;
-    o = (o + 15) & ~15;
-    L.wave0 = o;
-    int w = rcap * 8;                                    // prod: the product of the terms 1 + e of every survivor
-    w = (w + 15) & ~15;
-    // FPB1: per NON-EMPTY list of the window, in ion order, {first entry - first task, ion} (one more than ions: an idle
-    // lane may look at the entry behind the last); else per ion {first entry - first task, LDS offsets, frame} and, behind
-    // them, the ion of every non-empty list
-    L.o_ionrec = w; w += fpb1 ? (iw + 1) * 8 : iw * 16 + ((iw + 1 + 15) & ~15);
-    L.o_ttab = w; w += tt * 4;                           // landmark << (LG + 5) | ion of the window
-    L.o_sv = w; w += rcap * 4;                           // the task of every survivor
-    L.o_nzc = w; w += iw * 4;                            // entries written per ion
-    L.o_mark = w; w += mcap / 8 + 8;                     // a bit per candidate task of the window: set on the LAST task of every list
-    L.wbytes = (w + 15) & ~15;
-    L.total = L.wave0 + nw * L.wbytes;
-    return L;
-}
 
 // ---- arithmetic -----------------------------------------------------------------------------------------------------
 
@@ -1111,12 +1076,6 @@ __global__ __launch_bounds__(NW * 64) F3_WPE_ATTR void k_fill3(Fill3Head h, Fill
 
 // ---- host side ------------------------------------------------------------------------------------------------------
 
-static int f3_env_int(const char *name, int dflt)
-{
-    const char *e = getenv(name);
-    return e && *e ? atoi(e) : dflt;
-}
-
 // The reference zeroes a component when RN(RN(sqrt(d2)) / vcd) > rz for one of its vertices (helpers.pyx:176,197-199).
 // Both roundings are monotone in d2, so the decision is "d2 > T2" for T2 = the largest double that is not zeroed:
 // found by bisection over the (ordered) bit patterns of the non-negative doubles with the host's IEEE sqrt and division.
@@ -1309,17 +1268,18 @@ bool fill3_eligible(sit_ctx *c)
     return true;
 }
 
-// the instantiation for this cell / landmark width / waves per workgroup / mapping mode / frames per workgroup
-static hipError_t f3_dispatch(sit_ctx *c, const Fill3Head &h_in, Fill3ArgsPtr full, unsigned grid, size_t lds, int nw, int vp,
-                              bool diag, bool dynmap, bool fuse, bool slot)
+// the instantiation for this cell / landmark width / waves per workgroup / mapping mode / frames per workgroup, launched
+// (in.vp, in.diag, in.dynmap), launched with the plan's shape
+static hipError_t f3_dispatch(sit_ctx *c, const F3Plan &plan, const F3PlanIn &in, const Fill3Head &h_in, Fill3ArgsPtr full, unsigned grid)
 {
     Fill3Head h = h_in;
-    {
-        const int fpb1 = (nw != 4 || h.fpb == 1) ? 1 : 0;       // (as F3_PICK below)
-        const F3Layout L = f3_layout(fpb1 ? 1 : h.fpb, h.S + h.M, h.M, nw, h.rcap, h.iw, h.tt, h.mcap, fpb1);
-        const int v[12] = {L.fmax, L.gsync, L.ioninfo, L.etab, L.wave0, L.o_ionrec, L.o_ttab, L.o_sv, L.o_nzc, L.o_mark, L.wbytes, L.total};
-        for (int i = 0; i < 12; i++) h.lay[i] = v[i];
-    }
+    h.fpb = plan.fpb; h.iw = plan.iw; h.mcap = plan.mcap; h.rcap = plan.rcap; h.tt = plan.tt;
+    h.contig = plan.contig; h.prio = plan.prio; h.skipw = plan.skipw;
+    static_assert(sizeof(h.lay) == sizeof(F3Layout), "Fill3Head::lay is the F3Layout, field by field");
+    memcpy(h.lay, &plan.lay, sizeof(h.lay));
+    const size_t lds = plan.lds;
+    const int nw = plan.nw;
+    const bool dynmap = in.dynmap, fuse = plan.fuse, slot = plan.slot;
 #define F3_LAUNCH(CELL, LGV, NWV, DY, F1, DB, FU, SL)                                                                          \
     do {                                                                                                                   \
         hipError_t e = lds_limit((const void *)k_fill3<CELL, LGV, NWV, DY, F1, DB, FU, SL>, lds, c->device);               \
@@ -1338,21 +1298,15 @@ static hipError_t f3_dispatch(sit_ctx *c, const Fill3Head &h_in, Fill3ArgsPtr fu
 #define F3_PICK(CELL, LGV)                                                                                                     \
     do {                                                                                                                   \
         if (nw == 16) F3_PICK3(CELL, LGV, 16, 1); else if (nw == 8) F3_PICK3(CELL, LGV, 8, 1);                             \
-        else if (h.fpb == 1) F3_PICK3(CELL, LGV, 4, 1); else F3_PICK3(CELL, LGV, 4, 0);                                    \
+        else if (plan.fpb1) F3_PICK3(CELL, LGV, 4, 1); else F3_PICK3(CELL, LGV, 4, 0);                                     \
     } while (0)
-    if (diag) { if (vp == 16) F3_PICK(1, 4); else if (vp == 8) F3_PICK(1, 3); else F3_PICK(1, 2); }
-    else { if (vp == 16) F3_PICK(0, 4); else if (vp == 8) F3_PICK(0, 3); else F3_PICK(0, 2); }
+    if (in.diag) { if (in.vp == 16) F3_PICK(1, 4); else if (in.vp == 8) F3_PICK(1, 3); else F3_PICK(1, 2); }
+    else { if (in.vp == 16) F3_PICK(0, 4); else if (in.vp == 8) F3_PICK(0, 3); else F3_PICK(0, 2); }
 #undef F3_PICK
 #undef F3_PICK3
 #undef F3_LAUNCH
     return hipGetLastError();
 }
-
-// Survivor slots and task-table size of a wave depend on what the data does (C5 keeps six components per ion, C3
-// one): the first fill of a kind times the candidates on the leading frames and the process remembers the choice.
-struct F3Tuned { i64 key[8]; int rcap, tt; };
-static std::mutex g_f3_mutex;
-static std::vector<F3Tuned> g_f3_tuned;
 
 #define F3_ARGS_BYTES 1024          // the argument block; a copy for the trial launches and their counters sit behind it
 #define F3_TRIAL_WORDS 17
@@ -1370,25 +1324,13 @@ int fill3_prepare(sit_ctx *c)
     return SIT_OK;
 }
 
-int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64 f_hi, bool fuse, bool *fused)
+// The argument block and the by-value head of a launch, but for the shape (f3_dispatch puts the plan's into the head);
+// for a fused pass the wide-row list is carved from the scratch buffer, for the phase clocks their span sums
+static int f3_fill_args(sit_ctx *c, const sit_fill_params *p, const F3PlanIn &in, const F3Plan &plan, const F3Knobs &knobs, Fill3Args *ap, Fill3Head *hp)
 {
-    static_assert(sizeof(Fill3Args) <= F3_ARGS_BYTES, "argument block");
-    if (fused) *fused = false;
-    const bool fuse_asked = fuse;
-    if (f_hi < 0) f_hi = c->F;
-    const i64 S = c->S, M = c->M;
-    SIT_REQUIRE(c, c->D * f3_vp(c) < (1LL << 26) && c->F * S < (1LL << 40) && c->A < (1LL << 25), "sit_fill: sizes too large");
-    int rc = fill3_prepare(c);
-    if (rc) return rc;
-    const bool have_tight = c->tight_delta >= 0;
-    // the instantiations for a diagonal cell take the cheap distance (their list entries carry the widened threshold)
-    const bool diag = c->cell_diagonal && c->f3_cheap_ok && f3_env_int("SITATOR_F3_CHEAP", 1) != 0;
-    if ((rc = fill3_pack_lists(c, have_tight, diag))) return rc;
-    // the fused assignment: narrow CSC columns only (the dense fall-back of the assignment has no merge), no dynamic
-    // mapping, not an ablation run
-    if (fuse && (p->dynamic_lattice_mapping || c->K <= 0 || !c->d_col_ptr || c->max_col > 24 || c->N >= (1LL << 31) ||
-                 f3_env_int("SITATOR_DEBUG_STOP", 0))) fuse = false;
-    Fill3Args a;
+    Fill3Args &a = *ap;
+    Fill3Head &h = *hp;
+    const bool have_tight = in.have_tight;
     memset(&a, 0, sizeof(a));
     a.vh = (const uint4 *)c->d_vh; a.vh16 = (const uint4 *)c->d_vh16; a.nvtab = c->d_nv;
     a.pack = (const uint4 *)c->d_pack;
@@ -1396,7 +1338,7 @@ int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64
     a.f_base = (unsigned)c->pack_nt;
     if (have_tight) { a.p_off = c->d_tbin_off; a.pG0 = c->tG[0]; a.pG1 = c->tG[1]; a.pG2 = c->tG[2]; }
     else { a.p_off = c->d_bin_off; a.pG0 = c->G[0]; a.pG1 = c->G[1]; a.pG2 = c->G[2]; }
-    a.lattice_map = p->dynamic_lattice_mapping ? c->d_lattice_map : nullptr;
+    a.lattice_map = in.dynmap ? c->d_lattice_map : nullptr;
     a.row_nnz = c->d_row_nnz; a.row_idx = c->d_row_idx;
     a.N = c->N; a.D = (int)c->D; a.W = (int)c->rows_W;
     a.check_zeros = p->check_for_zeros;
@@ -1404,20 +1346,18 @@ int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64
     a.x0lo = c->f3_x0lo; a.x0hi = c->f3_x0hi;
     a.err = c->d_err; a.scal = c->d_scal; a.frame0 = c->frame0;
     for (int i = 0; i < 3; i++) a.cen[i] = c->pbc.cen[i];
-    if (f3_env_int("SITATOR_F3_FORCE_EXACT", 0)) { a.x0lo = -INFINITY; a.x0hi = INFINITY; }     // tests: every pass goes round again
-    a.nv_uniform = f3_env_int("SITATOR_F3_NVU", 1) ? c->nv_uniform : 0;
-    a.frame_mod = f3_env_int("SITATOR_F3_FRAME_MOD", 0);
+    if (knobs.force_exact) { a.x0lo = -INFINITY; a.x0hi = INFINITY; }
+    a.nv_uniform = knobs.nvu ? c->nv_uniform : 0;
+    a.frame_mod = knobs.frame_mod;
 
-    Fill3Head h;
     memset(&h, 0, sizeof(h));
     h.P = c->pbc; h.frames = c->d_frames; a.static_idx = c->d_static_idx; a.mobile_idx = c->d_mobile_idx;
     h.ref_static = c->d_ref_soa;
-    a.frame_dmax = p->dynamic_lattice_mapping ? c->d_frame_dmax : nullptr;
+    a.frame_dmax = in.dynmap ? c->d_frame_dmax : nullptr;
     h.exptab = c->d_exptab;
-    h.F = f_hi; h.fbeg = f_lo; h.A = c->A;
-    h.S = (int)S; h.M = (int)M;
-    const bool dynmap = a.lattice_map != nullptr;
-    h.debug_stop = dynmap ? 0 : f3_env_int("SITATOR_DEBUG_STOP", 0);
+    h.F = in.f_hi; h.fbeg = in.f_lo; h.A = c->A;
+    h.S = (int)in.S; h.M = (int)in.M;
+    h.debug_stop = f3_debug_stop(knobs, in.dynmap);
     h.has_fallback = have_tight ? 1 : 0;
     a.s0 = (int)c->idx_s0; a.m0 = (int)c->idx_m0;
     a.delta2 = have_tight ? c->tight_delta * c->tight_delta : -1.0;
@@ -1430,129 +1370,14 @@ int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64
         if (c->static_thr * (1.0 - 1e-9) < safe) safe = c->static_thr * (1.0 - 1e-9);
         h.safe2 = safe > 0 ? safe * safe * (1.0 - 1e-12) : -1.0;
     }
-    // launch shape: NW waves share the frames of a workgroup; every wave takes windows of IW of its ions
-    int nw = f3_env_int("SITATOR_FILL_WAVES", 0);
-    int fpb = f3_env_int("SITATOR_FILL_FPB", 0);
-    int rcap = f3_env_int("SITATOR_FILL_RCAP", 0);
-    const int vp = f3_vp(c);
-    int iw = f3_env_int("SITATOR_FILL_IW", 0);
-    if (fpb < 1) { i64 f = 64 / M; if (f < 1) f = 1; if (f > 32) f = 32; fpb = (int)f; }      // about 64 ions per workgroup
-    if (fpb > 32) fpb = 32;
-    const bool rcap_auto = rcap < 8 && !fuse;                  // fused: the list should hold a window's survivors (64 slots)
-    if (rcap < 8) rcap = 64;
-    rcap = (rcap + 7) / 8 * 8;
-    if (rcap > 64) rcap = 64;
-    if (rcap < 64 / vp) rcap = 64 / vp;                        // a pass of 64 / vp tasks must fit an empty region
-    const i64 wmax = have_tight ? std::max(c->W_tight, c->W) : c->W;       // longest candidate list an ion can meet
-    auto iw_for = [&](int nwv, int fpbv) {
-        // ions per wave window: the workgroup's ions dealt evenly, at least 16; at most 4096 candidate tasks
-        int v;
-        if (iw >= 1 && iw <= 64) v = (iw + 3) / 4 * 4;
-        else {
-            const i64 per = ((i64)fpbv * M + nwv - 1) / nwv;
-            v = (int)(per < 16 ? 16 : (per > 64 ? 64 : (per + 3) / 4 * 4));
-        }
-        while (v > 4 && (i64)v * wmax > 4096) v -= 4;
-        return v;
-    };
-    auto mcap_for = [&](int iwv) { return (int)(((i64)iwv * wmax + 63) / 64 * 64); };
-    // entries of a wave's task table (what passed the critical-vertex test and waits for its eight lanes): 128, more
-    // where the candidate lists are long (C3: 7 per ion, C5: 9)
-    int tt = f3_env_int("SITATOR_FILL_TCAP", 0);
-    const bool tt_auto = tt < 64 || tt > 1024;
-    if (tt_auto) tt = 128;
-    tt = (tt + 63) / 64 * 64;
-    const int lds_pad = f3_env_int("SITATOR_F3_LDS_PAD", 0);    // experiments: unused LDS per workgroup (fewer workgroups per CU)
-    auto lds_bytes = [&](int nwv, int fpbv, int rcapv) {
-        const int iwv = iw_for(nwv, fpbv);
-        return (size_t)f3_layout(fpbv, (int)(S + M), (int)M, nwv, rcapv, iwv, tt, mcap_for(iwv), fpbv == 1 ? 1 : 0).total + 32 + (size_t)lds_pad;
-    };
-    if (nw != 4 && nw != 8 && nw != 16) {
-        // Waves per workgroup: the count that keeps the most waves on a CU (workgroups are admitted by their LDS: the
-        // frame is shared by a workgroup's waves) among those that leave a wave a window of >= 32 ions (or what four
-        // waves would get, if that is less): C2 4 waves x 7 workgroups, C3 8 x 2 (12 % faster than 4 x 3), C4 8 x 2,
-        // C5 4 x 6.
-        while (fpb > 1 && lds_bytes(4, fpb, rcap) > 53 * 1024) fpb--;
-        auto per_wave = [&](int nwv) { const i64 v = ((i64)(nwv == 4 ? fpb : 1) * M + nwv - 1) / nwv; return v > 64 ? (i64)64 : v; };
-        int best = 4;
-        i64 best_waves = -1;
-        for (int nwv : {4, 8, 16}) {
-            // windows of >= 32 ions (16 for sixteen waves), or what four waves would get if that is less
-            const i64 want = std::min<i64>(nwv == 16 ? 16 : 32, per_wave(4));
-            if (per_wave(nwv) < want && nwv != 4) continue;
-            // resident waves: workgroups by their LDS (with fewer survivor slots if that admits one more, as below),
-            // whole workgroups within the register budget (seven waves per SIMD; eight for the sixteen-wave build)
-            i64 waves = -1;
-            for (int r : {rcap, 40, 32}) {
-                if (r != rcap && !(rcap_auto && r >= 64 / vp && r < rcap)) continue;
-                const size_t b = (lds_bytes(nwv, nwv == 4 ? fpb : 1, r) + 1535) / 1024 * 1024;
-                if (b > 160 * 1024) continue;
-                i64 wgs = (i64)((160 * 1024) / b);
-                if (wgs > 8) wgs = 8;
-                const i64 cap = (nwv == 16 ? 32 : 28) / nwv;
-                waves = std::max(waves, std::min(wgs, cap) * nwv);
-            }
-            if (waves > best_waves) { best_waves = waves; best = nwv; }
-        }
-        if (best_waves < 0) best = 16;                              // not even one workgroup of four or eight waves fits
-        nw = best;
-    }
-    if (nw != 4) fpb = 1;                                       // several frames per workgroup only with four waves
-    if (rcap_auto) {
-        // fewer survivor slots per wave when that admits one more workgroup per CU (a full region only costs a round)
-        // (workgroups are admitted with some slack: 5 x 31.5 KB did not run five per CU, 5 x 29.5 KB did)
-        auto wg_per_cu = [&](int r) {
-            const size_t b = (lds_bytes(nw, fpb, r) + 1535) / 1024 * 1024, cap = (size_t)((nw == 16 ? 32 : 28) / nw);   // LDS, registers
-            const size_t k = (160 * 1024) / b;
-            return k > cap ? cap : k;
-        };
-        for (int r : {40, 32}) if (r >= 64 / vp && wg_per_cu(r) > wg_per_cu(rcap)) rcap = r;
-    }
-    if (tt_auto) {
-        // the table should hold what a window's candidates leave behind: about half of (mean candidates per ion + 1) x
-        // ions, in steps of 64 up to 512, as long as that does not cost a workgroup per CU
-        const double per_ion = (have_tight ? c->tight_mean_candidates : c->mean_candidates) + 1.0;
-        int want = (int)(0.5 * per_ion * iw_for(nw, fpb)) + 64;
-        want = want < 128 ? 128 : (want > 512 ? 512 : (want + 63) / 64 * 64);
-        auto wgs = [&](int t) { const int keep = tt; tt = t; const size_t b = (lds_bytes(nw, fpb, rcap) + 1535) / 1024 * 1024; tt = keep; return (160 * 1024) / b; };
-        const size_t base = wgs(128);
-        int pick = 128;
-        for (int t = 192; t <= want; t += 64) if (wgs(t) == base) pick = t;
-        tt = pick;
-    }
-    while (fpb > 1 && lds_bytes(nw, fpb, rcap) > 160 * 1024 - 512) fpb--;
-    SIT_REQUIRE(c, lds_bytes(nw, fpb, rcap) <= 160 * 1024 - 256, "sit_fill: one frame's atoms do not fit in LDS");
-    iw = iw_for(nw, fpb);
-    SIT_REQUIRE(c, (i64)iw * wmax <= 65536, "sit_fill: candidate lists too long for the third-generation kernel");
-    h.fpb = fpb; h.iw = iw; h.mcap = mcap_for(iw);
-    // The slot form of the window (SLOT): possible with one frame per workgroup, lists of at most 64 entries in every table
-    // the launch can meet, no dynamic mapping and no ablation stop (the phase clocks have it).  Taken by default where it
-    // measured faster: four-wave workgroups whose primary table has no list longer than eight entries - every frame that
-    // stays on that table then runs eight slots per ion (C2: windows of 16 ions, two D0 passes in either form).
-    // SITATOR_F3_SLOT = 0 / 1 overrides the default where the form is possible.
-    bool slot = false;
-    {
-        const int dstop = p->dynamic_lattice_mapping ? 0 : f3_env_int("SITATOR_DEBUG_STOP", 0);
-        const bool possible = (nw != 4 || fpb == 1) && wmax <= 64 && !p->dynamic_lattice_mapping && (dstop == 0 || dstop >= 10);
-        const i64 wprim = have_tight ? c->W_tight : c->W;
-        const int asked = f3_env_int("SITATOR_F3_SLOT", -1);
-        slot = possible && (asked < 0 ? (nw == 4 && wprim <= 8) : asked != 0);
-        int width = 8;
-        while (width < wmax) width *= 2;
-        c->last_slot = slot ? width : 0;                        // the widest slots a window of this launch can take
-    }
-    // the fused assignment sits behind the window loop (and groups the windows of 64 / iw waves): one window per wave
-    if (fuse && (i64)fpb * M > (i64)nw * iw) fuse = false;
-    if (!fuse) store = true;                                    // the assignment kernels (if any) read the row buffers
-    a.row_val = fuse || store ? c->d_row_val : nullptr;
-    a.store = store ? 1 : 0;
-    const unsigned grid_all = (unsigned)((f_hi - f_lo + fpb - 1) / fpb);
-    int nseg = 0;
-    i64 seg_cap = 0;
-    if (fuse) {
+    a.row_val = plan.fuse || plan.store ? c->d_row_val : nullptr;
+    a.store = plan.store ? 1 : 0;
+    int rc;
+    if (plan.fuse) {
         // rows left to k_predict_rows_wide*: listed in nseg segments of the scratch buffer, workgroup b into segment b % nseg
-        nseg = (int)std::min<i64>((i64)grid_all > 0 ? (i64)grid_all : 1, (i64)cu_count(c) * 4);
-        seg_cap = ((i64)grid_all + nseg - 1) / nseg * ((i64)fpb * M);
+        const i64 grid_all = (i64)(unsigned)((in.f_hi - in.f_lo + plan.fpb - 1) / plan.fpb);
+        const int nseg = (int)std::min<i64>(grid_all > 0 ? grid_all : 1, (i64)cu_count(c) * 4);
+        const i64 seg_cap = (grid_all + nseg - 1) / nseg * ((i64)plan.fpb * in.M);
         if ((rc = wide_list_carve(c, nseg, seg_cap, &a.wcount, &a.wlist))) return rc;
         a.seg_cap = seg_cap; a.nseg = nseg;
         a.col_ptr = c->d_col_ptr; a.col_k = c->d_col_k; a.col_val = c->d_col_val;
@@ -1568,97 +1393,117 @@ int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64
         c->fill_args_host.assign((const char *)&a, (const char *)&a + sizeof(Fill3Args));
         HIP_TRY(c, hipMemcpyAsync(c->d_fill_args, c->fill_args_host.data(), sizeof(Fill3Args), hipMemcpyHostToDevice, c->stream));
     }
-    const Fill3ArgsPtr full = (Fill3ArgsPtr)c->d_fill_args;
-    int contig = c->idx_contig ? 1 : 0;
-    if (contig && c->idx_s0 == 0 && c->idx_m0 == S && c->A == S + M) contig = 2;
-    { const int forced = f3_env_int("SITATOR_FILL_CONTIG", -1); if (forced >= 0 && forced < contig) contig = forced; }
-    // 16-byte copies when every frame group of the launch starts on a 16-byte boundary and is an even number of doubles
-    {
-        const bool even_frame = ((S + M) * 3) % 2 == 0;
-        const bool even_groups = fpb % 2 == 0 && f_lo % 2 == 0 && (f_hi - f_lo) % fpb == 0;
-        if (contig == 2 && f3_env_int("SITATOR_FILL_WIDE_COPY", 1) && ((uintptr_t)c->d_frames % 16) == 0 && (even_frame || even_groups))
-            contig = 3;
-        // ... and by LDS-DMA (the last piece of a group may read 8 bytes past its frames: not past the buffer's last frame)
-        if (contig == 3 && f3_env_int("SITATOR_FILL_DMA", 1) && (even_frame || even_groups || f_hi < c->F)) contig = 4;
-    }
-    h.contig = contig;
-    h.prio = f3_env_int("SITATOR_F3_PRIO", 3);             // issue priority of phase 1 (0-3)
-    h.skipw = diag && !dynmap && c->f3_ref_in_cell && f3_env_int("SITATOR_F3_SKIPWRAP", 1) ? 1 : 0;
+    return SIT_OK;
+}
 
-    // ---- survivor slots / task-table size: measured once per kind of fill ----
-    if (rcap_auto && tt_auto && !fuse && h.debug_stop == 0 && f3_env_int("SITATOR_FILL_AUTOTUNE", 1) && (f_hi - f_lo) * M >= (1 << 18)) {
-        const i64 key[8] = {S, M, c->D, vp, have_tight ? c->W_tight : c->W, (i64)nw * 64 + fpb, dynmap ? 1 : 0, (i64)(c->tight_mean_candidates * 4.0 + 0.5)};   // candidates per ion in quarters: trajectories of one system share a key
-        bool found = false;
-        {
-            std::lock_guard<std::mutex> lock(g_f3_mutex);
-            for (const F3Tuned &t : g_f3_tuned) if (memcmp(t.key, key, sizeof(key)) == 0) { rcap = t.rcap; tt = t.tt; found = true; break; }
-        }
-        if (!found) {
-            const double per_ion = (have_tight ? c->tight_mean_candidates : c->mean_candidates) + 1.0;
-            int want = (int)(0.5 * per_ion * iw) + 64;
-            want = want < 128 ? 128 : (want > 512 ? 512 : (want + 63) / 64 * 64);
-            const int min_rcap = 64 / vp > 32 ? 64 / vp : 32;
-            const int NC = 5;
-            const int cand[NC][2] = {{rcap, tt}, {rcap, want}, {64, want}, {min_rcap, want}, {min_rcap, want > 256 ? 256 : want}};
-            // (destroyed on every way out of this block)
-            struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev0, ev1;
-            HIP_TRY(c, hipEventCreate(&ev0.e)); HIP_TRY(c, hipEventCreate(&ev1.e));
-            const hipEvent_t e0 = ev0.e, e1 = ev1.e;
-            // the trial launches write the rows of the leading frames (the launch proper writes them again) but report
-            // into words of their own: errors and counts of earlier launches of a pipelined call stay untouched
-            Fill3Head ht = h;
-            Fill3Args at = a;                                      // (a pageable copy: the call returns when it is staged)
-            at.err = (u64 *)(c->d_fill_args + 2 * F3_ARGS_BYTES); at.scal = at.err + 1;
-            HIP_TRY(c, hipMemsetAsync(at.err, 0, F3_TRIAL_WORDS * 8, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(c->d_fill_args + F3_ARGS_BYTES, &at, sizeof(Fill3Args), hipMemcpyHostToDevice, c->stream));
-            const Fill3ArgsPtr full_t = (Fill3ArgsPtr)(c->d_fill_args + F3_ARGS_BYTES);
-            ht.F = std::min<i64>(f_hi, f_lo + (i64)4096 * fpb);               // the leading frames: ~3 rounds of workgroups
-            const unsigned gt = (unsigned)((ht.F - f_lo + fpb - 1) / fpb);
-            float best = 1e30f;
-            int br = rcap, bt = tt;
-            const int keep_tt = tt;
-            for (int q = 0; q < NC; q++) {
-                bool dup = false;
-                for (int q2 = 0; q2 < q; q2++) dup = dup || (cand[q2][0] == cand[q][0] && cand[q2][1] == cand[q][1]);
-                if (dup) continue;
-                tt = cand[q][1];
-                const size_t ldq = lds_bytes(nw, fpb, cand[q][0]);
-                if (ldq > 160 * 1024 - 512) continue;
-                ht.rcap = cand[q][0]; ht.tt = cand[q][1];
-                float tq = 1e30f;
-                for (int rep = 0; rep < 5; rep++) {                            // the first launch of a shape warms it up; best of four
-                    HIP_TRY(c, hipEventRecord(e0, c->stream));
-                    HIP_TRY(c, f3_dispatch(c, ht, full_t, gt, ldq, nw, vp, diag, dynmap, false, slot));
-                    HIP_TRY(c, hipEventRecord(e1, c->stream));
-                    HIP_TRY(c, hipEventSynchronize(e1));
-                    float ms = 0;
-                    HIP_TRY(c, hipEventElapsedTime(&ms, e0, e1));
-                    if (rep > 0 && ms < tq) tq = ms;
-                }
-                if (tq < best * (q == 0 ? 1.0f : 0.96f)) { best = tq; br = cand[q][0]; bt = cand[q][1]; }   // the default wins ties (a 60 us trial has jitter)
-            }
-            tt = keep_tt;
-            rcap = br; tt = bt;
-            F3Tuned t; memcpy(t.key, key, sizeof(key)); t.rcap = rcap; t.tt = tt;
-            { std::lock_guard<std::mutex> lock(g_f3_mutex); g_f3_tuned.push_back(t); }
-        }
+// Survivor slots and task-table size of a wave depend on what the data does (C5 keeps six components per ion, C3
+// one): the first fill of a kind times the candidates on the leading frames and the process remembers the choice.
+struct F3Tuned { i64 key[8]; int rcap, tt; };
+static std::mutex g_f3_mutex;
+static std::vector<F3Tuned> g_f3_tuned;
+
+// survivor slots / task-table size: measured once per kind of fill (the plan comes back with the pair to run)
+static int f3_autotune(sit_ctx *c, const F3PlanIn &in, const F3Knobs &knobs, const Fill3Args &a, const Fill3Head &h, F3Plan *plan)
+{
+    const i64 key[8] = {in.S, in.M, c->D, in.vp, in.have_tight ? in.W_tight : in.W, (i64)plan->nw * 64 + plan->fpb, in.dynmap ? 1 : 0,
+                        (i64)(c->tight_mean_candidates * 4.0 + 0.5)};   // candidates per ion in quarters: trajectories of one system share a key
+    {
+        std::lock_guard<std::mutex> lock(g_f3_mutex);
+        for (const F3Tuned &t : g_f3_tuned) if (memcmp(t.key, key, sizeof(key)) == 0) { *plan = f3_plan_with(*plan, t.rcap, t.tt); return SIT_OK; }
     }
-    const size_t lds = lds_bytes(nw, fpb, rcap);
-    SIT_REQUIRE(c, lds <= 160 * 1024 - 256, "sit_fill: one frame's atoms do not fit in LDS");
-    h.rcap = rcap; h.tt = tt;
-    if (f3_env_int("SITATOR_DEBUG_SHAPE", 0))
-        fprintf(stderr, "k_fill3 shape: nw %d fpb %d rcap %d iw %d tt %d mcap %d, %zu bytes of LDS per workgroup\n", nw, fpb, rcap, iw, tt, h.mcap, lds);
-    c->last_fpb = fpb; c->last_kernel = 3; c->last_iw = rcap; c->last_nw = nw; c->last_tt = tt;
-    const unsigned grid = (unsigned)((f_hi - f_lo + fpb - 1) / fpb);
-    if (fused) *fused = fuse;
-    c->last_fused = fuse;
-    if (fuse) {
+    // (destroyed on every way out of this function)
+    struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev0, ev1;
+    HIP_TRY(c, hipEventCreate(&ev0.e)); HIP_TRY(c, hipEventCreate(&ev1.e));
+    // the trial launches write the rows of the leading frames (the launch proper writes them again) but report
+    // into words of their own: errors and counts of earlier launches of a pipelined call stay untouched
+    Fill3Head ht = h;
+    Fill3Args at = a;                                      // (a pageable copy: the call returns when it is staged)
+    at.err = (u64 *)(c->d_fill_args + 2 * F3_ARGS_BYTES); at.scal = at.err + 1;
+    HIP_TRY(c, hipMemsetAsync(at.err, 0, F3_TRIAL_WORDS * 8, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_fill_args + F3_ARGS_BYTES, &at, sizeof(Fill3Args), hipMemcpyHostToDevice, c->stream));
+    const Fill3ArgsPtr full_t = (Fill3ArgsPtr)(c->d_fill_args + F3_ARGS_BYTES);
+    ht.F = std::min<i64>(in.f_hi, in.f_lo + (i64)4096 * plan->fpb);      // the leading frames: ~3 rounds of workgroups
+    const unsigned gt = (unsigned)((ht.F - in.f_lo + plan->fpb - 1) / plan->fpb);
+    float best = 1e30f;
+    std::pair<int, int> pick(plan->rcap, plan->tt);
+    for (const std::pair<int, int> &q : f3_tune_candidates(*plan, in)) {
+        const F3Plan trial = f3_plan_with(*plan, q.first, q.second);
+        if (knobs.debug_shape) fprintf(stderr, "k_fill3 trial: rcap %d tt %d, %zu bytes of LDS per workgroup\n", trial.rcap, trial.tt, trial.lds);
+        float tq = 1e30f;
+        for (int rep = 0; rep < 5; rep++) {                            // the first launch of a shape warms it up; best of four
+            HIP_TRY(c, hipEventRecord(ev0.e, c->stream));
+            HIP_TRY(c, f3_dispatch(c, trial, in, ht, full_t, gt));
+            HIP_TRY(c, hipEventRecord(ev1.e, c->stream));
+            HIP_TRY(c, hipEventSynchronize(ev1.e));
+            float ms = 0;
+            HIP_TRY(c, hipEventElapsedTime(&ms, ev0.e, ev1.e));
+            if (rep > 0 && ms < tq) tq = ms;
+        }
+        const bool own = q.first == plan->rcap && q.second == plan->tt;
+        if (tq < best * (own ? 1.0f : 0.96f)) { best = tq; pick = q; }   // the default wins ties (a 60 us trial has jitter)
+    }
+    *plan = f3_plan_with(*plan, pick.first, pick.second);
+    F3Tuned t; memcpy(t.key, key, sizeof(key)); t.rcap = plan->rcap; t.tt = plan->tt;
+    { std::lock_guard<std::mutex> lock(g_f3_mutex); g_f3_tuned.push_back(t); }
+    return SIT_OK;
+}
+
+// what the decision looks at, from the context and the call
+static F3PlanIn f3_plan_in(sit_ctx *c, const sit_fill_params *p, const F3Knobs &knobs, bool store, i64 f_lo, i64 f_hi, bool fuse)
+{
+    F3PlanIn in;
+    in.S = c->S; in.M = c->M; in.vp = f3_vp(c);
+    in.W = c->W; in.W_tight = c->W_tight; in.have_tight = c->tight_delta >= 0;
+    in.mean_candidates = c->mean_candidates; in.tight_mean_candidates = c->tight_mean_candidates;
+    in.dynmap = p->dynamic_lattice_mapping != 0;             // (sit_fill has launched k_lattice_map: the map is there)
+    // the fused assignment: narrow CSC columns only (the dense fall-back of the assignment has no merge), no dynamic
+    // mapping, not an ablation run
+    in.fuse_asked = fuse;
+    in.fuse_ok = !(p->dynamic_lattice_mapping || c->K <= 0 || !c->d_col_ptr || c->max_col > 24 || c->N >= (1LL << 31) || knobs.debug_stop);
+    in.store = store; in.f_lo = f_lo; in.f_hi = f_hi; in.F = c->F;
+    in.idx_contig = c->idx_contig; in.idx_s0 = c->idx_s0; in.idx_m0 = c->idx_m0; in.A = c->A;
+    in.frames_aligned16 = ((uintptr_t)c->d_frames % 16) == 0;
+    // the instantiations for a diagonal cell take the cheap distance (their list entries carry the widened threshold)
+    in.diag = c->cell_diagonal && c->f3_cheap_ok && knobs.cheap != 0;
+    in.f3_ref_in_cell = c->f3_ref_in_cell;
+    return in;
+}
+
+int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo, i64 f_hi, bool fuse, bool *fused)
+{
+    static_assert(sizeof(Fill3Args) <= F3_ARGS_BYTES, "argument block");
+    if (fused) *fused = false;
+    if (f_hi < 0) f_hi = c->F;
+    SIT_REQUIRE(c, c->D * f3_vp(c) < (1LL << 26) && c->F * c->S < (1LL << 40) && c->A < (1LL << 25), "sit_fill: sizes too large");
+    int rc = fill3_prepare(c);
+    if (rc) return rc;
+    const F3Knobs knobs = f3_knobs_from_env();
+    const F3PlanIn in = f3_plan_in(c, p, knobs, store, f_lo, f_hi, fuse);
+    if ((rc = fill3_pack_lists(c, in.have_tight, in.diag))) return rc;
+    F3Plan plan = f3_plan(in, knobs);
+    SIT_REQUIRE(c, !plan.err, plan.err);
+    c->last_slot = plan.slot_width;
+    Fill3Args a;
+    Fill3Head h;
+    if ((rc = f3_fill_args(c, p, in, plan, knobs, &a, &h))) return rc;
+    if (plan.rcap_auto && plan.tt_auto && !plan.fuse && h.debug_stop == 0 && knobs.autotune && (f_hi - f_lo) * in.M >= (1 << 18)) {
+        if ((rc = f3_autotune(c, in, knobs, a, h, &plan))) return rc;
+        SIT_REQUIRE(c, !plan.err, plan.err);                    // (a pair remembered from a launch with another LDS pad)
+    }
+    if (knobs.debug_shape)
+        fprintf(stderr, "k_fill3 shape: nw %d fpb %d rcap %d iw %d tt %d mcap %d, %zu bytes of LDS per workgroup\n", plan.nw, plan.fpb, plan.rcap,
+                plan.iw, plan.tt, plan.mcap, plan.lds);
+    c->last_fpb = plan.fpb; c->last_kernel = 3; c->last_rcap = plan.rcap; c->last_nw = plan.nw; c->last_tt = plan.tt;
+    const unsigned grid = (unsigned)((f_hi - f_lo + plan.fpb - 1) / plan.fpb);
+    if (fused) *fused = plan.fuse;
+    c->last_fused = plan.fuse;
+    if (plan.fuse) {
         // the error words, the label counts and the lengths of the list's segments, in one launch ahead of the kernel
-        if ((rc = reset_step_words(c, true, a.wcount, 2 * nseg))) return rc;
-        c->fuse_wlist = a.wlist; c->fuse_wcount = a.wcount; c->fuse_seg_cap = seg_cap; c->fuse_nseg = nseg;
-    } else if (fuse_asked && (rc = reset_fill_words(c))) return rc;   // a caller that asks for the fused pass leaves the reset to it
+        if ((rc = reset_step_words(c, true, a.wcount, 2 * a.nseg))) return rc;
+        c->fuse_wlist = a.wlist; c->fuse_wcount = a.wcount; c->fuse_seg_cap = a.seg_cap; c->fuse_nseg = a.nseg;
+    } else if (fuse && (rc = reset_fill_words(c))) return rc;   // a caller that asks for the fused pass leaves the reset to it
     if (f_hi <= f_lo) return SIT_OK;
-    HIP_TRY(c, f3_dispatch(c, h, full, grid, lds, nw, vp, diag, dynmap, fuse, slot));
+    HIP_TRY(c, f3_dispatch(c, plan, in, h, (Fill3ArgsPtr)c->d_fill_args, grid));
     if (h.debug_stop >= 10) { k_f3_spans<<<dim3(1), dim3(64), 0, c->stream>>>(a.dbgbuf, c->d_scal); HIP_TRY(c, hipGetLastError()); }
     return SIT_OK;
 }

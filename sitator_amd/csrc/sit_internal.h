@@ -79,7 +79,7 @@ struct sit_ctx {
     bool idx_contig = false;          // static_idx / mobile_idx are consecutive atom ranges
     i64 idx_s0 = 0, idx_m0 = 0;
     double hmin = 0;                  // smallest perpendicular height of the cell
-    int last_kernel = 0, last_iw = 0, last_nw = 0, last_tt = 0;
+    int last_kernel = 0, last_rcap = 0, last_nw = 0, last_tt = 0;
     int nv_uniform = 0;               // > 0: every landmark has this many vertices
     i64 band_redos = 0;               // k_fill3 on diagonal cells: pass groups of the last fill that went round again with the reference's arithmetic
     bool f3_ref_in_cell = false;      // every reference position within [-0.25, 1.25) of the cell (k_fill3 may leave statics unwrapped)
