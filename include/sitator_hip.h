@@ -144,7 +144,7 @@ typedef struct sit_fill_params {
  * its result is collected: sit_fill_result waits for every pass in flight and returns the first failure (with *err) -
  * once; a later sit_fill returns a failure that has landed meanwhile INSTEAD of running - once; and every entry point
  * that READS what a pass produces (rows, labels, counts: sit_predict, sit_get_assignments, sit_get_rows_*, sit_gram*,
- * sit_weighted_row_sums*, sit_best_match*, sit_fit_push_stored_rows, sit_site_*, sit_check_occupancy, sit_jump_*,
+ * sit_weighted_row_sums*, sit_best_match*, sit_fit_push_stored_rows, sit_site_*, sit_check_occupancy, sit_cooccupancy, sit_jump_*,
  * sit_assign_last_known, sit_running_mode, sit_count_zero_rows) first waits for the passes in flight and returns their
  * first failure instead of the output of a failed pass (the failure stays until sit_fill_result or sit_fill has
  * reported it).  sit_synchronize waits and decodes but returns the HIP status only.  sit_set_frames /
@@ -241,6 +241,14 @@ int sit_check_occupancy(sit_ctx *ctx, int64_t K, int64_t max_per_site,
 /* np.bincount(traj[traj >= 0], minlength=K) of the device labels: compute_site_occupancies (:187-202) divides it
  * by the number of frames.                                                                */
 int sit_site_counts(sit_ctx *ctx, int64_t K, int64_t *counts);
+
+/* co[a*K + b] = 1 iff some frame of the resident labels has one ion on site a and one on site b
+ * (a == b: the site is occupied at all); 0 otherwise.  Labels < 0 are ignored; a label >= K fails the
+ * way sit_jump_analysis does (SIT_ERR_INVALID, message starting "index ", IndexError in Python).
+ * MergeSitesByThreshold.py:64-70 clears exactly these entries.  One pass over the labels plus
+ * (label changes) x M byte stores, not M^2 per frame.  K <= 16384 (the matrix is K*K bytes, on the
+ * device too: 256 MB at the limit); no frames: all zeros.                                        */
+int sit_cooccupancy(sit_ctx *ctx, int64_t K, uint8_t *co);
 
 /* Upload a label array (and optional confidences) as the context's assignments, for a
  * SiteTrajectory that was not produced on this context (SiteTrajectory.__init__, :15-42).

@@ -88,6 +88,7 @@ SIGNATURES = {
     "sit_check_occupancy": (C.c_int, [_vp, i64, i64, _ip, _ip, _ip, C.POINTER(SitError)]),
     "sit_set_assignments": (C.c_int, [_vp, _ip, _dp, i64, i64, i64]),
     "sit_site_counts": (C.c_int, [_vp, i64, _ip]),
+    "sit_cooccupancy": (C.c_int, [_vp, i64, _u8p]),
     "sit_jump_sources": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip]),
     "sit_jump_list": (C.c_int, [_vp, C.c_int, _ip, i64, _ip, _ip, _ip]),
     "sit_jump_analysis": (C.c_int, [_vp, i64, _ip, _ip, _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
@@ -540,6 +541,18 @@ class HipContext(object):
         self._check(self.lib.sit_site_counts(self._h, int(K), _i(counts)))
         return counts
 
+    def cooccupancy(self, K):
+        """``bool[K, K]``: entry (a, b) says whether some resident frame has one ion on site a and one on site b
+        (``sit_cooccupancy``; at most 16384 sites)."""
+        K = int(K)
+        co = np.zeros((K, K), dtype=np.uint8)
+        rc = self.lib.sit_cooccupancy(self._h, K, co.ctypes.data_as(_u8p))
+        if rc == E_INVALID and self.message().startswith("index "):
+            # a label beyond the sites: the reference's connmat[site, frame] raises this (MergeSitesByThreshold.py:70)
+            raise IndexError(self.message())
+        self._check(rc)
+        return co.view(np.bool_)
+
     JUMP_NONE = -(1 << 63)
 
     def jump_sources(self, unknown_as_jump=False, last_known_in=None):
@@ -717,7 +730,7 @@ def _settling(fn):
 
 for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "assignments", "count_zero_rows", "gram",
               "gram_limbs", "weighted_row_sums", "weighted_row_sums_limbs", "best_match", "best_match_groups",
-              "site_anchors", "site_sums", "check_occupancy", "site_counts", "jump_sources", "jump_list",
+              "site_anchors", "site_sums", "check_occupancy", "site_counts", "cooccupancy", "jump_sources", "jump_list",
               "jump_analysis", "assign_last_known", "running_mode", "set_centers"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

@@ -2,6 +2,7 @@
 // util/PBCCalculator.pyx:106-139) and SiteTrajectory.check_multiple_occupancy
 // (SiteTrajectory.py:205-232) on the device-resident labels / confidences.
 #include <cmath>
+#include <cstdio>
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
 #include "sit_internal.h"
@@ -292,6 +293,81 @@ extern "C" int sit_check_occupancy(sit_ctx *c, i64 K, i64 max_per_site, i64 *n_m
     if (key != SIT_NO_ERROR_KEY) {
         if (err) { err->kind = SIT_ERR_MULTIPLE_OCCUPANCY; err->frame = (i64)(key / (u64)K); err->index = (i64)(key % (u64)K); }
         return SIT_ERR_MULTIPLE_OCCUPANCY;
+    }
+    return SIT_OK;
+}
+
+// ---- co-occupancy (dynamics/MergeSitesByThreshold.py:64-70) -----------------------------------
+// co[a,b] = 1 iff some frame has one ion on site a and one on site b.  The reference clears an M x M block per frame;
+// here only CHANGES are paired: a pair (a,b) held in frame f by ions i and j was already held in frame f-1 unless i or j
+// changed its label at f, so it is enough to pair every ion whose known label differs from its label one frame earlier
+// (in frame 0 of the context: every known ion) with all known ions of its frame - one streaming read of the labels plus
+// (label changes) x M scattered byte stores.  The previous frame is read from global memory, so the first frame of a
+// workgroup's block is like any other.  Every writer stores the same byte (an OR: order-independent, bit-reproducible),
+// so plain byte stores into the zeroed matrix do, without atomics.  A workgroup takes CO_FRAMES_PER_WG consecutive
+// frames, a wave every fourth of them; the changed ions of a wave's 64 are taken one at a time (ballot) and each is
+// paired by the whole wave.  A label >= K is written nowhere: the smallest one goes to *err and the call fails with it.
+#define CO_FRAMES_PER_WG 64
+__global__ __launch_bounds__(256) void k_cooccupancy(const i64 *labels, i64 F, i64 M, i64 K, u64 *err, unsigned char *co)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const i64 f0 = (i64)blockIdx.x * CO_FRAMES_PER_WG;
+    const i64 f1 = f0 + CO_FRAMES_PER_WG < F ? f0 + CO_FRAMES_PER_WG : F;
+    for (i64 f = f0 + wave; f < f1; f += 4) {
+        const i64 *row = labels + f * M;
+        for (i64 base = 0; base < M; base += 64) {
+            const i64 j = base + lane;
+            i64 cur = -1;
+            bool moved = false;
+            if (j < M) {
+                cur = row[j];
+                const i64 prev = f > 0 ? row[j - M] : -1;        // (both loads in flight before either is looked at)
+                if (cur >= K) { atomicMin(err, (u64)cur); cur = -1; }
+                moved = cur >= 0 && (f == 0 || prev != cur);
+            }
+            unsigned long long todo = __ballot(moved);          // the same in every lane: the loop below is wave-uniform
+            while (todo) {
+                const int src = __ffsll((long long)todo) - 1;
+                todo &= todo - 1ull;
+                const i64 a = __shfl(cur, src);
+                for (i64 q = lane; q < M; q += 64) {
+                    const i64 b = row[q];
+                    if (b >= 0 && b < K) { co[a * K + b] = 1; co[b * K + a] = 1; }
+                }
+            }
+        }
+    }
+}
+
+#define CO_MAX_SITES 16384          // the K x K byte matrix: 256 MB of device scratch and of the caller's memory
+extern "C" int sit_cooccupancy(sit_ctx *c, i64 K, uint8_t *co)
+{
+    if (!c || !co) return SIT_ERR_INVALID;
+    SIT_SETTLE(c);
+    SIT_REQUIRE(c, c->assign_valid && K > 0, "sit_cooccupancy: assignments needed");
+    SIT_REQUIRE(c, K <= CO_MAX_SITES, "sit_cooccupancy: more than 16384 sites (the K x K matrix is limited to 256 MB)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_scratch(c, K * K);
+    if (rc) return rc;
+    unsigned char *d_co = (unsigned char *)c->d_scratch;
+    HIP_TRY(c, hipMemsetAsync(c->d_err, 0xFF, sizeof(u64), c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_co, 0, (size_t)(K * K), c->stream));
+    StageTimer t(c, T_OCC);
+    if (c->F > 0) {
+        k_cooccupancy<<<dim3((unsigned)((c->F + CO_FRAMES_PER_WG - 1) / CO_FRAMES_PER_WG)), dim3(256), 0, c->stream>>>(
+            c->d_labels, c->F, c->M, K, c->d_err, d_co);
+        HIP_TRY(c, hipGetLastError());
+    }
+    t.stop();
+    u64 key = 0;
+    HIP_TRY(c, hipMemcpyAsync(&key, c->d_err, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(co, d_co, (size_t)(K * K), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (key != SIT_NO_ERROR_KEY) {
+        char text[128];
+        snprintf(text, sizeof(text), "index %lld is out of bounds for axis 0 with size %lld", (long long)key, (long long)K);
+        c->msg = text;
+        return SIT_ERR_INVALID;
     }
     return SIT_OK;
 }

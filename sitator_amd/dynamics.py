@@ -5,8 +5,13 @@ device-resident site assignments:
 * ``SmoothSiteTrajectory``  (reference ``sitator/dynamics/SmoothSiteTrajectory.pyx:13-111``)
 * ``MergeSitesByDynamics``  (reference ``sitator/dynamics/MergeSitesByDynamics.py:12-153``; host logic over the jump
   statistics, distances and averages through the device-backed ``PBCCalculator``)
+* ``MergeSitesByThreshold``  (reference ``sitator/dynamics/MergeSitesByThreshold.py:11-87``; the co-occupancy matrix of
+  ``forbid_multiple_occupancy`` comes from the device labels)
+* ``RemoveUnoccupiedSites``  (reference ``sitator/dynamics/RemoveUnoccupiedSites.py:10-71``; the visit counts come from
+  the device labels)
 """
 import logging
+import operator
 
 import numpy as np
 
@@ -225,3 +230,83 @@ class MergeSitesByDynamics(MergeSites):
                            "  This may or may not be a problem; but if `distance_threshold` is low, consider raising it."
                            % n_alarming_ignored_edges)
         return markov_clustering(connectivity_matrix, **self.markov_parameters)   # :153
+
+
+class MergeSitesByThreshold(MergeSites):
+    """Merges the connected components of the graph that a strict threshold on any edge attribute leaves (reference
+    ``dynamics/MergeSitesByThreshold.py``).  The threshold is a keyword of ``run()``: ``run(st, threshold=0)``.
+
+    ``attrname``: the edge attribute (``n_ij``, ``p_ij``, ``jump_lag``, ...); ``relation``: applied as
+    ``relation(attribute, threshold)``; ``directed`` / ``connection``: passed to ``scipy.sparse.csgraph``'s
+    ``connected_components``; ``distance_threshold``: sites further apart than this (Angstrom) are not connected;
+    ``forbid_multiple_occupancy``: sites that were ever occupied in the same frame are not connected (the matrix of
+    ``SiteTrajectory.compute_site_cooccupancy``, one pass of the device over the labels where the reference walks the
+    frames); further keywords go to ``MergeSites``."""
+
+    def __init__(self, attrname, relation=operator.ge, directed=True, connection='strong', distance_threshold=np.inf,
+                 forbid_multiple_occupancy=False, **kwargs):
+        self.attrname = attrname
+        self.relation = relation
+        self.directed = directed
+        self.connection = connection
+        self.distance_threshold = distance_threshold
+        self.forbid_multiple_occupancy = forbid_multiple_occupancy
+        super(MergeSitesByThreshold, self).__init__(**kwargs)
+
+    def _get_sites_to_merge(self, st, threshold=0):
+        from scipy.sparse.csgraph import connected_components
+        sn = st.site_network
+        n_sites = sn.n_sites
+        attrmat = np.asarray(getattr(sn, self.attrname))
+        assert attrmat.shape == (n_sites, n_sites), "`attrname` doesn't seem to indicate an edge property."
+        connmat = np.array(self.relation(attrmat, threshold), copy=True)     # never the attribute itself (:50)
+        if self.distance_threshold < np.inf:                                 # :53-62
+            pbcc = PBCCalculator(np.asarray(sn.structure.cell, dtype=np.float64))
+            centers = np.asarray(sn.centers)
+            for i in range(n_sites - 1):
+                js_too_far = np.where(pbcc.distances(centers[i], centers[i + 1:]) > self.distance_threshold)[0] + i + 1
+                connmat[i, js_too_far] = False
+                connmat[js_too_far, i] = False
+        if self.forbid_multiple_occupancy:                                   # :64-70
+            connmat[st.compute_site_cooccupancy()] = False
+        np.fill_diagonal(connmat, True)                                      # :73
+        n_merged_sites, labels = connected_components(connmat, directed=self.directed, connection=self.connection)
+        return [np.where(labels == lbl)[0] for lbl in range(n_merged_sites)]
+
+
+class RemoveUnoccupiedSites(object):
+    """Drops the sites no particle is ever assigned to and renumbers the rest in order (reference
+    ``dynamics/RemoveUnoccupiedSites.py``).  Which sites are visited is read from the device-resident labels
+    (``sit_site_counts``; summed over the ranks on frame shards)."""
+
+    def __init__(self):
+        pass
+
+    def run(self, st, return_kept_sites=False):
+        """A ``SiteTrajectory`` over the visited sites: types, vertices, site and edge attributes of the kept sites
+        are carried over (``old_sn[seen_mask]``, :60), the confidences are not, the real trajectory is.  With
+        ``return_kept_sites``: ``(new_st, np.where(seen_mask))``.  When every site is visited ``st`` ITSELF is
+        returned - alone, also with ``return_kept_sites=True``, as the reference does (:31-34)."""
+        assert isinstance(st, SiteTrajectory)
+        old_sn = st.site_network
+        n_sites = int(old_sn.n_sites)
+        counts = st._device().site_counts(n_sites) if n_sites > 0 else np.zeros(0, dtype=np.int64)
+        comm = st._comm
+        if comm is not None and comm.size > 1:
+            counts = comm.allreduce_sum(counts)
+        seen_mask = counts > 0
+        if np.all(seen_mask):
+            return st
+        logger.info("Removing unoccupied sites %s" % np.where(~seen_mask)[0])
+        n_new_sites = int(np.sum(seen_mask))
+        if n_new_sites < old_sn.n_mobile:                                    # :42-47
+            raise errors.InsufficientSitesError(verb="Removing unoccupied sites", n_sites=n_new_sites,
+                                                n_mobile=old_sn.n_mobile)
+        translation = np.full(n_sites + 1, SiteTrajectory.SITE_UNKNOWN, dtype=np.int64)   # [-1]: unknown stays unknown
+        translation[:-1][seen_mask] = np.arange(n_new_sites)
+        new_st = SiteTrajectory(old_sn[seen_mask], translation[st._traj], confidences=None, _adopt=True)
+        if st.real_trajectory is not None:
+            new_st.set_real_traj(st.real_trajectory)
+        if return_kept_sites:
+            return new_st, np.where(seen_mask)
+        return new_st

@@ -172,6 +172,21 @@ class SiteTrajectory(object):
         self._sn.add_site_attribute("occupancies", occ)
         return occ
 
+    def compute_site_cooccupancy(self):
+        """``bool[n_sites, n_sites]``: entry (a, b) says whether some frame has one mobile particle on site a and one
+        on site b (the diagonal: the site is occupied at all) - the entries ``MergeSitesByThreshold`` with
+        ``forbid_multiple_occupancy`` refuses to connect (reference ``dynamics/MergeSitesByThreshold.py:64-70``).
+        Computed from the device-resident labels; on frame shards the ranks' matrices are ORed (a rank's first frame
+        pairs all its particles, so a shard needs nothing of its neighbour).  Nothing is stored on the network."""
+        n_sites = int(self._sn.n_sites)
+        if n_sites == 0:
+            return np.zeros((0, 0), dtype=bool)
+        co = self._device().cooccupancy(n_sites)
+        comm = self._comm
+        if comm is not None and comm.size > 1:
+            co = np.logical_or.reduce(comm.allgather(co), axis=0)
+        return co
+
     # -- device-backed pieces ----------------------------------------------------------------
     def _device(self):
         """A context holding this trajectory's CURRENT labels: a fresh upload if there is no context yet, and again
