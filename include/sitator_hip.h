@@ -285,6 +285,35 @@ int sit_assign_last_known(sit_ctx *ctx, int64_t frame_threshold, const int64_t *
                           const int64_t *time_unknown_in, int64_t *labels_out, int32_t *frame_max,
                           int64_t *stats3, int64_t *last_known_out, int64_t *time_unknown_out);
 
+/* ReplaceUnassignedPositions (dynamics/ReplaceUnassignedPositions.py:90-117) on the device-resident labels, which are
+ * only read.  "Unknown" is label == -1; for an unknown frame `before` is the nearest label != -1 at an earlier frame of
+ * the ion, failing that before_in[ion], failing that -1; `after` the same towards later frames.  before_in / after_in
+ * ([M], both or neither; NULL = -1) are what frame shards carry in from their neighbours.
+ *
+ * sit_label_ends: per ion the first and the last label != -1 of this context's frames, INT64_MIN where it has none:
+ * all that frame shards exchange.                                                                              */
+int sit_label_ends(sit_ctx *ctx, int64_t *first_known, int64_t *last_known);
+/* labels_out[F*M]: the labels with every unknown frame replaced by `before` (mode 0) or by `after` (mode 1).       */
+int sit_replace_unassigned(sit_ctx *ctx, int mode, const int64_t *before_in, const int64_t *after_in,
+                           int64_t *labels_out);
+/* Every maximal run of unknown frames as a record {ion, start, end, before, after, pos_offset} of int64, ion-major and
+ * by start within an ion (the order the reference calls its replacement function in, :99-112; the same on every call).
+ * start / end (exclusive) are global frame numbers inside this context's frames.  pos_offset: the running sum of the
+ * lengths of the runs whose before and after are both >= 0 and differ (those the closer-site strategy has to decide),
+ * -1 for the other runs; *n_positions is that sum.  *n_records is the number found; when it exceeds max_records
+ * nothing is written - call again with a larger buffer.                                                          */
+int sit_unknown_runs(sit_ctx *ctx, const int64_t *before_in, const int64_t *after_in, int64_t max_records,
+                     int64_t *records, int64_t *n_records, int64_t *n_positions);
+/* replace_with_closer (:56-87) for records of the layout above: positions[n_positions][3] holds the real-space position
+ * of the run's ion at every frame of every run with pos_offset >= 0, in record order; such a frame becomes `before`
+ * when dist(position, centers[before]) < dist(position, centers[after]) (the shift-and-wrap distance of sit_distances)
+ * and `after` otherwise.  Runs with before == after >= 0 take that site, runs with a side of -1 stay -1, every other
+ * entry of labels_out[F*M] is the resident label.  The records are checked before anything is indexed with them: a site
+ * >= K fails like sit_jump_analysis (SIT_ERR_INVALID, message starting "index ", IndexError in Python); an ion outside
+ * [0, M), frames outside the context, a site < -1 or positions outside [0, n_positions) fail with SIT_ERR_INVALID.   */
+int sit_replace_closer(sit_ctx *ctx, const int64_t *records, int64_t n, const double *centers, int64_t K,
+                       const double *positions, int64_t n_positions, int64_t *labels_out);
+
 /* running_windowed_mode (dynamics/SmoothSiteTrajectory.pyx:79-111) of the device labels -> out[F*M]; counts
  * (optional, [K]) = np.bincount of the smoothed labels >= 0: which sites are left occupied
  * (dynamics/RemoveUnoccupiedSites.py:31-38 looks for the others).                                        */

@@ -93,6 +93,10 @@ SIGNATURES = {
     "sit_jump_list": (C.c_int, [_vp, C.c_int, _ip, i64, _ip, _ip, _ip]),
     "sit_jump_analysis": (C.c_int, [_vp, i64, _ip, _ip, _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
     "sit_assign_last_known": (C.c_int, [_vp, i64, _ip, _ip, _ip, _i32p, _ip, _ip, _ip]),
+    "sit_label_ends": (C.c_int, [_vp, _ip, _ip]),
+    "sit_replace_unassigned": (C.c_int, [_vp, C.c_int, _ip, _ip, _ip]),
+    "sit_unknown_runs": (C.c_int, [_vp, _ip, _ip, i64, _ip, _ip, _ip]),
+    "sit_replace_closer": (C.c_int, [_vp, _ip, i64, _dp, i64, _dp, i64, _ip]),
     "sit_running_mode": (C.c_int, [_vp, i64, i64, i64, C.c_int, _ip, i64, _ip]),
     "sit_recenter_resident": (C.c_int, [_vp, _dp, _dp, _dp]),
     "sit_recenter": (C.c_int, [_vp, _dp, i64, i64, _dp, _dp, _dp]),
@@ -612,6 +616,65 @@ class HipContext(object):
                                                    fmax.ctypes.data_as(_i32p), _i(st), _i(lout), _i(tout)))
         return labels, fmax[:self.F], st, lout, tout
 
+    # -- ReplaceUnassignedPositions: the resident labels are read, never written (labels_version stays)
+    ENDS_NONE = -(1 << 63)
+
+    def _halo_pair(self, before_in, after_in):
+        if (before_in is None) != (after_in is None):
+            raise ValueError("before_in and after_in come as a pair")
+        if before_in is None:
+            return None, None
+        b, a = _i64(before_in), _i64(after_in)
+        assert b.shape == (self.M,) and a.shape == (self.M,)
+        return b, a
+
+    def label_ends(self):
+        """Per ion the first and the last label != -1 of this context's frames (``ENDS_NONE`` where it has none)."""
+        first = np.full(self.M, self.ENDS_NONE, dtype=np.int64)
+        last = np.full(self.M, self.ENDS_NONE, dtype=np.int64)
+        self._check(self.lib.sit_label_ends(self._h, _i(first), _i(last)))
+        return first, last
+
+    def replace_unassigned(self, mode, before_in=None, after_in=None):
+        """The labels with every -1 replaced by the nearest known label before it (``mode`` 0) or after it (1);
+        ``before_in`` / ``after_in`` ([M]): what holds before the first and after the last frame (default -1)."""
+        b, a = self._halo_pair(before_in, after_in)
+        out = np.empty((self.F, self.M), dtype=np.int64)
+        self._check(self.lib.sit_replace_unassigned(self._h, int(mode), None if b is None else _i(b),
+                                                    None if a is None else _i(a), _i(out)))
+        return out
+
+    def unknown_runs(self, before_in=None, after_in=None):
+        """``(records, n_positions)``: every maximal run of -1 as (ion, start, end, before, after, pos_offset), ion-major
+        and by start; start / end are global frame numbers (``sit_unknown_runs``)."""
+        b, a = self._halo_pair(before_in, after_in)
+        cap = 1 << 16
+        while True:
+            rec = np.empty((cap, 6), dtype=np.int64)
+            n, npos = i64(0), i64(0)
+            self._check(self.lib.sit_unknown_runs(self._h, None if b is None else _i(b), None if a is None else _i(a),
+                                                  cap, _i(rec), C.byref(n), C.byref(npos)))
+            if n.value <= cap:
+                break
+            cap = int(n.value)
+        return rec[:n.value], int(npos.value)
+
+    def replace_closer(self, records, centers, positions):
+        """The labels with the runs of ``records`` (as ``unknown_runs`` gives them) filled by the closer-site rule;
+        ``positions`` [n_positions, 3]: the ion's real-space position at every frame of the runs with an offset.  A site
+        beyond ``centers`` raises ``IndexError``, any other record that does not fit the context ``ValueError``."""
+        records = _i64(records).reshape(-1, 6)
+        centers = _f64(centers).reshape(-1, 3)
+        positions = _f64(positions).reshape(-1, 3)
+        out = np.empty((self.F, self.M), dtype=np.int64)
+        rc = self.lib.sit_replace_closer(self._h, _i(records), len(records), _d(centers), len(centers), _d(positions),
+                                         len(positions), _i(out))
+        if rc == E_INVALID and self.message().startswith("index "):
+            # a label beyond the sites: the reference's centers[before_site] raises this (ReplaceUnassignedPositions.py:75)
+            raise IndexError(self.message())
+        self._check(rc)
+        return out
+
     def running_mode(self, wleft, wright, threshold, replace_unknown, n_sites=0):
         """The smoothed labels, and (``n_sites`` > 0) how often every site occurs among them."""
         out = np.empty((self.F, self.M), dtype=np.int64)
@@ -731,6 +794,7 @@ def _settling(fn):
 for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "assignments", "count_zero_rows", "gram",
               "gram_limbs", "weighted_row_sums", "weighted_row_sums_limbs", "best_match", "best_match_groups",
               "site_anchors", "site_sums", "check_occupancy", "site_counts", "cooccupancy", "jump_sources", "jump_list",
-              "jump_analysis", "assign_last_known", "running_mode", "set_centers"):
+              "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
+              "unknown_runs", "replace_closer"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

@@ -1,6 +1,7 @@
 // The steps either side of the landmark path, on the device-resident label array:
 //   JumpAnalysis.run                         dynamics/JumpAnalysis.py:27-135
 //   SiteTrajectory.assign_to_last_known_site SiteTrajectory.py:235-304
+//   ReplaceUnassignedPositions.run           dynamics/ReplaceUnassignedPositions.py:90-117
 //   SmoothSiteTrajectory.running_windowed_mode   dynamics/SmoothSiteTrajectory.pyx:79-111
 //   RecenterTrajectory.run                   util/RecenterTrajectory.pyx:14-100
 #include <cmath>
@@ -293,6 +294,364 @@ extern "C" int sit_assign_last_known(sit_ctx *c, i64 frame_threshold, const i64 
     if (time_unknown_out) HIP_TRY(c, hipMemcpyAsync(time_unknown_out, d_tout, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     stats3[0] = (i64)st[0]; stats3[1] = (i64)st[1]; stats3[2] = (i64)st[2];
+    return SIT_OK;
+}
+
+// ---- ReplaceUnassignedPositions (dynamics/ReplaceUnassignedPositions.py:90-117) ---------------------------
+// Every unknown frame of an ion needs the nearest known label BEFORE it and the nearest AFTER it: the scan of k_alk_*
+// run in both directions.  (1) every (chunk, ion) summarises its chunk: first and last known label and where the first
+// one is; (2) one lane per ion chains the summaries forwards (`before` at every chunk's start) and backwards (`after`
+// at every chunk's end, and the frame it was found at: where a run that leaves the chunk ends); (3) every (chunk, ion)
+// replays its chunk.  The resident labels are only read.
+__global__ __launch_bounds__(64) void k_rup_chunk_summary(const i64 *labels, i64 F, i64 M, i64 *first_known, i64 *last_known,
+                                                          i32 *first_pos)
+{
+    const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
+    if (j >= M) return;
+    const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
+    i64 fk = D_NONE, lk = D_NONE;
+    i32 fp = -1;
+    for (i64 f = f0; f < f1; f++) {
+        const i64 cur = labels[f * M + j];
+        if (cur == -1) continue;
+        if (fp < 0) { fk = cur; fp = (i32)(f - f0); }
+        lk = cur;
+    }
+    first_known[c * M + j] = fk; last_known[c * M + j] = lk; first_pos[c * M + j] = fp;
+}
+
+// carry_before[c]: the label a run that starts chunk c has before it; carry_after[c] / carry_end[c]: the label after a
+// run that reaches the end of chunk c and the (local) frame that label stands at (F: none).  ends[0..M) / ends[M..2M):
+// first and last known label of the ion in these frames (D_NONE: none) - without the values carried in.
+__global__ void k_rup_chunk_carry(i64 F, i64 M, i64 nch, const i64 *before_in, const i64 *after_in, const i64 *first_known,
+                                  const i64 *last_known, const i32 *first_pos, i64 *carry_before, i64 *carry_after,
+                                  i64 *carry_end, i64 *ends)
+{
+    const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    i64 before = before_in ? before_in[j] : -1, last = D_NONE;
+    for (i64 c = 0; c < nch; c++) {
+        carry_before[c * M + j] = before;
+        const i64 lk = last_known[c * M + j];
+        if (lk != D_NONE) before = last = lk;
+    }
+    i64 after = after_in ? after_in[j] : -1, end = F, first = D_NONE;
+    for (i64 c = nch - 1; c >= 0; c--) {
+        carry_after[c * M + j] = after; carry_end[c * M + j] = end;
+        const i32 fp = first_pos[c * M + j];
+        if (fp >= 0) { after = first = first_known[c * M + j]; end = c * DCH + fp; }
+    }
+    ends[j] = first; ends[M + j] = last;
+}
+
+// mode 0: forwards, every unknown frame takes `before`; mode 1: backwards, it takes `after`
+__global__ __launch_bounds__(64) void k_rup_chunk_replay(const i64 *labels, i64 F, i64 M, int mode, const i64 *carry_before,
+                                                         const i64 *carry_after, i64 *out)
+{
+    const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
+    if (j >= M) return;
+    const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
+    if (mode == 0) {
+        i64 fill = carry_before[c * M + j];
+        for (i64 f = f0; f < f1; f++) {
+            const i64 cur = labels[f * M + j];
+            if (cur != -1) fill = cur;
+            out[f * M + j] = fill;
+        }
+    } else {
+        i64 fill = carry_after[c * M + j];
+        for (i64 f = f1 - 1; f >= f0; f--) {
+            const i64 cur = labels[f * M + j];
+            if (cur != -1) fill = cur;
+            out[f * M + j] = fill;
+        }
+    }
+}
+
+// The maximal runs of unknown frames that START in chunk c of ion j.  EMIT = false counts them and the positions they
+// ask for (runs whose two sides are known and differ); EMIT = true writes them from the offsets the scan made of the
+// counts.  A run that reaches the chunk's end takes its end and `after` from the backward carry.
+template <bool EMIT>
+__global__ __launch_bounds__(64) void k_rup_runs(const i64 *labels, i64 F, i64 M, i64 frame0, const i64 *carry_before,
+                                                 const i64 *carry_after, const i64 *carry_end, i64 *n_runs, i64 *n_pos,
+                                                 i64 *rec)
+{
+    const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
+    if (j >= M) return;
+    const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
+    i64 before = carry_before[c * M + j];
+    i64 runs = EMIT ? n_runs[c * M + j] : 0, pos = EMIT ? n_pos[c * M + j] : 0;
+    bool open = f0 > 0 && labels[(f0 - 1) * M + j] == -1;        // a run of an earlier chunk is still going
+    i64 start = -1;
+    for (i64 f = f0; f <= f1; f++) {
+        const i64 cur = f < f1 ? labels[f * M + j] : 0;
+        if (f < f1 && cur == -1) {
+            if (!open && start < 0) start = f;
+            continue;
+        }
+        if (start >= 0) {
+            const i64 end = f < f1 ? f : carry_end[c * M + j];
+            const i64 after = f < f1 ? cur : carry_after[c * M + j];
+            const bool decide = before >= 0 && after >= 0 && before != after;
+            if (EMIT) {
+                i64 *r = rec + 6 * runs;
+                r[0] = j; r[1] = frame0 + start; r[2] = frame0 + end; r[3] = before; r[4] = after; r[5] = decide ? pos : -1;
+            }
+            runs++;
+            if (decide) pos += end - start;
+            start = -1;
+        }
+        open = false;
+        before = cur;
+    }
+    if (!EMIT) { n_runs[c * M + j] = runs; n_pos[c * M + j] = pos; }
+}
+
+// Exclusive prefix sums of the two count tables in ION-MAJOR order (item i = j * nch + c lives at [c * M + j]): the
+// reference walks the ions, and the runs of an ion in frame order (:99-112).  One workgroup: the tables have F * M / DCH
+// entries.  totals[0], totals[1]: the sums.
+__global__ __launch_bounds__(1024) void k_rup_scan(i64 *n_runs, i64 *n_pos, i64 M, i64 nch, i64 *totals)
+{
+    __shared__ i64 sr[1024], sp[1024];
+    const i64 T = M * nch, per = (T + 1023) / 1024;
+    const i64 i0 = (i64)threadIdx.x * per, i1 = i0 + per < T ? i0 + per : T;
+    i64 r = 0, p = 0;
+    for (i64 i = i0; i < i1; i++) { const i64 o = (i % nch) * M + i / nch; r += n_runs[o]; p += n_pos[o]; }
+    sr[threadIdx.x] = r; sp[threadIdx.x] = p;
+    __syncthreads();
+    for (int s = 1; s < 1024; s <<= 1) {                           // inclusive scan of the threads' sums
+        const i64 ar = (int)threadIdx.x >= s ? sr[threadIdx.x - s] : 0, ap = (int)threadIdx.x >= s ? sp[threadIdx.x - s] : 0;
+        __syncthreads();
+        sr[threadIdx.x] += ar; sp[threadIdx.x] += ap;
+        __syncthreads();
+    }
+    i64 br = sr[threadIdx.x] - r, bp = sp[threadIdx.x] - p;
+    for (i64 i = i0; i < i1; i++) {
+        const i64 o = (i % nch) * M + i / nch;
+        const i64 nr = n_runs[o], np = n_pos[o];
+        n_runs[o] = br; n_pos[o] = bp;
+        br += nr; bp += np;
+    }
+    if (threadIdx.x == 1023) { totals[0] = sr[1023]; totals[1] = sp[1023]; }
+}
+
+// scratch of the two-directional scan: the three launches every entry point below starts with
+struct RupScan {
+    i64 *before_in, *after_in, *fk, *lk, *cb, *ca, *ce, *ends;
+    i32 *fp;
+    char *rest;
+};
+
+static i64 rup_scan_bytes(i64 M, i64 nch) { return 4 * M * 8 + nch * M * 44 + 64; }
+
+static int rup_scan(sit_ctx *c, char *p, const i64 *before_in, const i64 *after_in, RupScan *s)
+{
+    const i64 M = c->M, F = c->F, nch = (F + DCH - 1) / DCH;
+    s->before_in = (i64 *)p; p += M * 8;
+    s->after_in = (i64 *)p; p += M * 8;
+    s->ends = (i64 *)p; p += 2 * M * 8;
+    s->fk = (i64 *)p; p += nch * M * 8;
+    s->lk = (i64 *)p; p += nch * M * 8;
+    s->cb = (i64 *)p; p += nch * M * 8;
+    s->ca = (i64 *)p; p += nch * M * 8;
+    s->ce = (i64 *)p; p += nch * M * 8;
+    s->fp = (i32 *)p; p += nch * M * 4;
+    p += (8 - ((size_t)p & 7)) & 7;
+    s->rest = p;
+    if (M == 0) return SIT_OK;
+    if (before_in) {
+        HIP_TRY(c, hipMemcpyAsync(s->before_in, before_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(s->after_in, after_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+    }
+    const unsigned gy = (unsigned)((M + 63) / 64);
+    if (nch > 0) k_rup_chunk_summary<<<dim3((unsigned)nch, gy), dim3(64), 0, c->stream>>>(c->d_labels, F, M, s->fk, s->lk, s->fp);
+    k_rup_chunk_carry<<<dim3(gy), dim3(64), 0, c->stream>>>(F, M, nch, before_in ? s->before_in : nullptr,
+                                                          before_in ? s->after_in : nullptr, s->fk, s->lk, s->fp, s->cb, s->ca,
+                                                          s->ce, s->ends);
+    HIP_TRY(c, hipGetLastError());
+    return SIT_OK;
+}
+
+extern "C" int sit_label_ends(sit_ctx *c, i64 *first_known, i64 *last_known)
+{
+    if (!c || !first_known || !last_known) return SIT_ERR_INVALID;
+    SIT_SETTLE(c);
+    SIT_REQUIRE(c, c->assign_valid, "sit_label_ends: assignments needed");
+    const i64 M = c->M, nch = (c->F + DCH - 1) / DCH;
+    if (M == 0) return SIT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_scratch(c, rup_scan_bytes(M, nch));
+    if (rc) return rc;
+    RupScan s;
+    if ((rc = rup_scan(c, (char *)c->d_scratch, nullptr, nullptr, &s))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(first_known, s.ends, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(last_known, s.ends + M, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SIT_OK;
+}
+
+extern "C" int sit_replace_unassigned(sit_ctx *c, int mode, const i64 *before_in, const i64 *after_in, i64 *labels_out)
+{
+    if (!c || !labels_out) return SIT_ERR_INVALID;
+    SIT_SETTLE(c);
+    SIT_REQUIRE(c, c->assign_valid, "sit_replace_unassigned: assignments needed");
+    SIT_REQUIRE(c, mode == 0 || mode == 1, "sit_replace_unassigned: mode is 0 (last known) or 1 (next known)");
+    SIT_REQUIRE(c, (before_in == nullptr) == (after_in == nullptr), "sit_replace_unassigned: the carried-in arrays come in pairs");
+    const i64 M = c->M, F = c->F, N = c->N, nch = (F + DCH - 1) / DCH;
+    if (N == 0) return SIT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_scratch(c, rup_scan_bytes(M, nch) + N * 8);
+    if (rc) return rc;
+    RupScan s;
+    if ((rc = rup_scan(c, (char *)c->d_scratch, before_in, after_in, &s))) return rc;
+    i64 *d_out = (i64 *)s.rest;
+    k_rup_chunk_replay<<<dim3((unsigned)nch, (unsigned)((M + 63) / 64)), dim3(64), 0, c->stream>>>(c->d_labels, F, M, mode, s.cb,
+                                                                                                 s.ca, d_out);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(labels_out, d_out, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SIT_OK;
+}
+
+extern "C" int sit_unknown_runs(sit_ctx *c, const i64 *before_in, const i64 *after_in, i64 max_records, i64 *records,
+                                i64 *n_records, i64 *n_positions)
+{
+    if (!c || !n_records || !n_positions || (max_records > 0 && !records)) return SIT_ERR_INVALID;
+    SIT_SETTLE(c);
+    SIT_REQUIRE(c, c->assign_valid && max_records >= 0, "sit_unknown_runs: assignments needed");
+    SIT_REQUIRE(c, (before_in == nullptr) == (after_in == nullptr), "sit_unknown_runs: the carried-in arrays come in pairs");
+    const i64 M = c->M, F = c->F, nch = (F + DCH - 1) / DCH;
+    *n_records = 0; *n_positions = 0;
+    if (c->N == 0) return SIT_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_scratch(c, rup_scan_bytes(M, nch) + 2 * nch * M * 8 + 16 + max_records * 48);
+    if (rc) return rc;
+    RupScan s;
+    if ((rc = rup_scan(c, (char *)c->d_scratch, before_in, after_in, &s))) return rc;
+    i64 *d_nr = (i64 *)s.rest, *d_np = d_nr + nch * M, *d_tot = d_np + nch * M, *d_rec = d_tot + 2;
+    const dim3 cgrid((unsigned)nch, (unsigned)((M + 63) / 64));
+    k_rup_runs<false><<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, c->frame0, s.cb, s.ca, s.ce, d_nr, d_np, nullptr);
+    k_rup_scan<<<dim3(1), dim3(1024), 0, c->stream>>>(d_nr, d_np, M, nch, d_tot);
+    HIP_TRY(c, hipGetLastError());
+    i64 *h_tot = (i64 *)c->h_pinned;
+    HIP_TRY(c, hipMemcpyAsync(h_tot, d_tot, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *n_records = h_tot[0]; *n_positions = h_tot[1];
+    if (h_tot[0] == 0 || h_tot[0] > max_records) return SIT_OK;
+    k_rup_runs<true><<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, c->frame0, s.cb, s.ca, s.ce, d_nr, d_np, d_rec);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(records, d_rec, (size_t)h_tot[0] * 48, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SIT_OK;
+}
+
+// The closer-site strategy (:56-87) on records the CALLER hands in.  k_rc_check looks at every record before anything is
+// indexed with it: flags[0] = records that break a bound, flags[1] = largest label >= K, + 1.
+__global__ __launch_bounds__(256) void k_rc_check(const i64 *rec, i64 n, i64 F, i64 M, i64 frame0, i64 K, i64 n_positions, u64 *flags)
+{
+    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const i64 ion = rec[6 * r], start = rec[6 * r + 1], end = rec[6 * r + 2], before = rec[6 * r + 3], after = rec[6 * r + 4],
+              off = rec[6 * r + 5];
+    bool bad = ion < 0 || ion >= M || start < frame0 || start >= end || end > frame0 + F || before < -1 || after < -1;
+    if (before >= K || after >= K) atomicMax(&flags[1], (u64)(before > after ? before : after) + 1ull);
+    else if (!bad && before >= 0 && after >= 0 && before != after)
+        bad = off < 0 || off > n_positions - (end - start);
+    if (bad) atomicAdd(&flags[0], 1ull);
+}
+
+// Lane per (checked) record: a run whose two sides are the same site takes it; a run to decide marks its positions with
+// its own number for k_rc_decide.  Only frames that ARE unknown in the resident labels are written.
+__global__ __launch_bounds__(256) void k_rc_expand(const i64 *rec, i64 n, const i64 *labels, i64 M, i64 frame0, i64 *owner, i64 *out)
+{
+    const i64 r = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    const i64 ion = rec[6 * r], start = rec[6 * r + 1] - frame0, end = rec[6 * r + 2] - frame0, before = rec[6 * r + 3],
+              after = rec[6 * r + 4], off = rec[6 * r + 5];
+    if (before < 0 || after < 0) return;
+    if (before == after) {
+        for (i64 f = start; f < end; f++)
+            if (labels[f * M + ion] == -1) out[f * M + ion] = before;
+    } else {
+        for (i64 i = 0; i < end - start; i++) owner[off + i] = r;
+    }
+}
+
+// Lane per (run, frame of the run) to decide: `before` if the position is strictly nearer to its centre, else `after`
+__global__ __launch_bounds__(256) void k_rc_decide(Pbc P, const i64 *rec, const i64 *owner, i64 n_positions, const double *pos,
+                                                   const double *centers, const i64 *labels, i64 M, i64 frame0, i64 *out)
+{
+    const i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_positions) return;
+    const i64 r = owner[p];
+    if (r < 0) return;
+    const i64 ion = rec[6 * r], before = rec[6 * r + 3], after = rec[6 * r + 4];
+    const i64 f = rec[6 * r + 1] - frame0 + (p - rec[6 * r + 5]);
+    if (labels[f * M + ion] != -1) return;
+    const double x = pos[3 * p], y = pos[3 * p + 1], z = pos[3 * p + 2];
+    const double db = dist_sw(P, x, y, z, centers[3 * before], centers[3 * before + 1], centers[3 * before + 2]);
+    const double da = dist_sw(P, x, y, z, centers[3 * after], centers[3 * after + 1], centers[3 * after + 2]);
+    out[f * M + ion] = db < da ? before : after;                  // :83-86
+}
+
+extern "C" int sit_replace_closer(sit_ctx *c, const i64 *records, i64 n, const double *centers, i64 K, const double *positions,
+                                  i64 n_positions, i64 *labels_out)
+{
+    if (!c || !labels_out) return SIT_ERR_INVALID;
+    SIT_SETTLE(c);
+    SIT_REQUIRE(c, c->assign_valid, "sit_replace_closer: assignments needed");
+    SIT_REQUIRE(c, n >= 0 && K >= 0 && n_positions >= 0, "sit_replace_closer: negative count");
+    SIT_REQUIRE(c, (n == 0 || records) && (K == 0 || centers) && (n_positions == 0 || positions), "sit_replace_closer: missing array");
+    const i64 M = c->M, F = c->F, N = c->N;
+    if (N == 0) {
+        SIT_REQUIRE(c, n == 0, "sit_replace_closer: records for a context without frames");
+        return SIT_OK;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = ensure_scratch(c, 64 + N * 8 + n * 48 + n_positions * 8 + K * 24 + n_positions * 24);
+    if (rc) return rc;
+    char *p = (char *)c->d_scratch;
+    u64 *d_flags = (u64 *)p; p += 64;
+    i64 *d_out = (i64 *)p; p += N * 8;
+    i64 *d_rec = (i64 *)p; p += n * 48;
+    i64 *d_owner = (i64 *)p; p += n_positions * 8;
+    double *d_cen = (double *)p; p += K * 24;
+    double *d_pos = (double *)p;
+    HIP_TRY(c, hipMemcpyAsync(d_out, c->d_labels, (size_t)N * 8, hipMemcpyDeviceToDevice, c->stream));
+    if (n > 0) {
+        HIP_TRY(c, hipMemsetAsync(d_flags, 0, 64, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d_rec, records, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
+        k_rc_check<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(d_rec, n, F, M, c->frame0, K, n_positions, d_flags);
+        HIP_TRY(c, hipGetLastError());
+        u64 *h_flags = (u64 *)c->h_pinned;
+        HIP_TRY(c, hipMemcpyAsync(h_flags, d_flags, 16, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (h_flags[1]) {
+            char text[128];
+            snprintf(text, sizeof(text), "index %lld is out of bounds for axis 0 with size %lld", (long long)h_flags[1] - 1, (long long)K);
+            c->msg = text;
+            return SIT_ERR_INVALID;
+        }
+        if (h_flags[0]) {
+            char text[160];
+            snprintf(text, sizeof(text), "sit_replace_closer: %llu records outside the context (ion, frames, sites or position offset)",
+                     (unsigned long long)h_flags[0]);
+            c->msg = text;
+            return SIT_ERR_INVALID;
+        }
+        if (K > 0) HIP_TRY(c, hipMemcpyAsync(d_cen, centers, (size_t)K * 24, hipMemcpyHostToDevice, c->stream));
+        if (n_positions > 0) {
+            HIP_TRY(c, hipMemcpyAsync(d_pos, positions, (size_t)n_positions * 24, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemsetAsync(d_owner, 0xFF, (size_t)n_positions * 8, c->stream));
+        }
+        k_rc_expand<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(d_rec, n, c->d_labels, M, c->frame0, d_owner, d_out);
+        if (n_positions > 0)
+            k_rc_decide<<<dim3((unsigned)((n_positions + 255) / 256)), dim3(256), 0, c->stream>>>(
+                c->pbc, d_rec, d_owner, n_positions, d_pos, d_cen, c->d_labels, M, c->frame0, d_out);
+        HIP_TRY(c, hipGetLastError());
+    }
+    HIP_TRY(c, hipMemcpyAsync(labels_out, d_out, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SIT_OK;
 }
 

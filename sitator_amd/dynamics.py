@@ -9,6 +9,8 @@ device-resident site assignments:
   ``forbid_multiple_occupancy`` comes from the device labels)
 * ``RemoveUnoccupiedSites``  (reference ``sitator/dynamics/RemoveUnoccupiedSites.py:10-71``; the visit counts come from
   the device labels)
+* ``ReplaceUnassignedPositions``  (reference ``sitator/dynamics/ReplaceUnassignedPositions.py:26-117``; the nearest known
+  label before and after every unassigned frame comes from a two-directional scan of the device labels)
 """
 import logging
 import operator
@@ -310,3 +312,154 @@ class RemoveUnoccupiedSites(object):
         if return_kept_sites:
             return new_st, np.where(seen_mask)
         return new_st
+
+
+class _ReplaceWithCloser(object):
+    """What ``ReplaceUnassignedPositions.replace_with_closer()`` returns: a replacement function that gives each frame of
+    an unassigned run to whichever of the sites before and after the run the ion is closer to in real space."""
+
+    def __init__(self):
+        self._pbcc = None
+        self._cell = None
+
+    def __call__(self, st, mobile_atom, before_site, start_frame, after_site, end_frame):
+        if before_site == SiteTrajectory.SITE_UNKNOWN or after_site == SiteTrajectory.SITE_UNKNOWN:
+            return SiteTrajectory.SITE_UNKNOWN
+        if st.real_trajectory is None:
+            raise ValueError("replace_with_closer needs a SiteTrajectory with a real trajectory (set_real_traj)")
+        sn = st.site_network
+        cell = np.asarray(sn.structure.cell, dtype=np.float64)
+        if self._pbcc is None or not np.array_equal(cell, self._cell):
+            self._pbcc, self._cell = PBCCalculator(cell), cell.copy()
+        atom = np.where(sn.mobile_mask)[0][mobile_atom]
+        two = np.asarray(sn.centers)[[before_site, after_site]]
+        out = np.empty(end_frame - start_frame, dtype=np.int64)
+        for i in range(len(out)):
+            d = self._pbcc.distances(st.real_trajectory[start_frame + i, atom], two)
+            out[i] = before_site if d[0] < d[1] else after_site            # :83-86: a tie goes to the site after
+        return out
+
+
+def shard_halo(first_known, last_known, rank, none=-(1 << 63)):
+    """``(before_in, after_in)`` of frame shard ``rank`` from the gathered ``label_ends()`` of all shards
+    (``first_known`` / ``last_known``: ``[n_shards, n_mobile]``, ``none`` where a shard has no known label of the ion):
+    per ion the last known label of the nearest lower shard that has one and the first known label of the nearest higher
+    shard that has one, -1 where there is none."""
+    first_known, last_known = np.asarray(first_known), np.asarray(last_known)
+    M = first_known.shape[1]
+    before = np.full(M, SiteTrajectory.SITE_UNKNOWN, dtype=np.int64)
+    after = np.full(M, SiteTrajectory.SITE_UNKNOWN, dtype=np.int64)
+    for r in range(rank):                                   # ascending: a nearer shard overwrites a further one
+        has = last_known[r] != none
+        before[has] = last_known[r][has]
+    for r in range(len(first_known) - 1, rank, -1):
+        has = first_known[r] != none
+        after[has] = first_known[r][has]
+    return before, after
+
+
+class ReplaceUnassignedPositions(object):
+    """Fills the runs of unassigned frames of every mobile ion from the sites on either side of the run (reference
+    ``dynamics/ReplaceUnassignedPositions.py``).  ``run(st)`` returns a new ``SiteTrajectory``; ``st``, its label array
+    and the labels resident on the device stay as they are.
+
+    ``replacement_function``: a callable ``(st, mobile_atom, before_site, start_frame, after_site, end_frame)`` that
+    returns one site for the whole run or an array of ``end_frame - start_frame`` sites.  ``before_site`` /
+    ``after_site`` are the nearest labels other than ``SITE_UNKNOWN`` (-1 exactly) before and after the run,
+    ``SITE_UNKNOWN`` where the trajectory begins or ends with the run.  The three strategies of the reference are
+    recognised and evaluated by HIP kernels over the device-resident labels, without a pass of the host over the label
+    array: ``replace_with_last_known``, ``replace_with_next_known`` (one call each) and the callable that
+    ``replace_with_closer()`` makes (the runs come back as records, the positions of the frames to decide are gathered
+    from ``st.real_trajectory`` with one fancy index, the decision is made on the device).  Any other callable is called
+    once per run, ion by ion and in frame order, as the reference calls it.
+
+    Deviations from the reference, whose own copy is barely usable:
+
+    * ``None`` means ``replace_with_last_known``.  The reference's default reads an undefined ``RemoveShortJumps``
+      (:42): ``ReplaceUnassignedPositions()`` raises ``NameError`` there.
+    * ``replace_with_closer()`` returns a working callable.  The reference's returns ``None`` (:56-87: the inner
+      function is never returned, and it assigns ``pbcc`` without ``nonlocal``).  The rule is that of its docstring and
+      inner body: a frame goes to ``before_site`` when the ion is strictly closer to that centre (shift-and-wrap distance
+      of ``PBCCalculator.distances``), otherwise to ``after_site``; a run with an unknown side stays unknown.  The ion's
+      position is that of atom ``where(mobile_mask)[mobile_atom]`` of the real trajectory (the inner body indexes the
+      real trajectory with the mobile-atom number itself, which is the ion only where the mobile atoms come first).  It
+      raises ``ValueError`` without a real trajectory and ``IndexError`` for a label ``>= n_sites``; a label below -1
+      is not wrapped round as numpy's indexing would, the device path refuses it with ``ValueError``.
+
+    The result is ``st.copy(with_computed=False)`` of the reference with the new labels (:114-117): the confidences and
+    the real trajectory are carried over; NO site or edge attribute is, computed or not - the reference's
+    ``SiteNetwork.copy`` re-adds every attribute as "computed" (``SiteNetwork.py:116-123``) before it clears those, and
+    the goldens record exactly that.
+
+    On frame shards every rank calls ``label_ends()`` once, the ranks gather the two vectors and each derives what holds
+    before its first and after its last frame (``shard_halo``); the three built-in strategies then run locally.  Another
+    callable raises ``NotImplementedError`` there: a run would be cut at the ends of the shards."""
+
+    def __init__(self, replacement_function=None):
+        if replacement_function is None:
+            replacement_function = ReplaceUnassignedPositions.replace_with_last_known
+        assert callable(replacement_function)
+        self.replacement_function = replacement_function
+
+    @staticmethod
+    def replace_with_last_known(st, mobile_atom, before_site, start_frame, after_site, end_frame):
+        """Replace unassigned with the last known site."""
+        return before_site
+
+    @staticmethod
+    def replace_with_next_known(st, mobile_atom, before_site, start_frame, after_site, end_frame):
+        """Replace unassigned with the next known site."""
+        return after_site
+
+    @staticmethod
+    def replace_with_closer():
+        """Makes the function that assigns each position of an unassigned run to whichever of the sites before and after
+        it is closer to in real space."""
+        return _ReplaceWithCloser()
+
+    def run(self, st):
+        assert isinstance(st, SiteTrajectory)
+        fn = self.replacement_function
+        sn = st.site_network
+        ctx = st._device()
+        comm = st._comm
+        before_in = after_in = None
+        builtin = (fn is ReplaceUnassignedPositions.replace_with_last_known
+                   or fn is ReplaceUnassignedPositions.replace_with_next_known or isinstance(fn, _ReplaceWithCloser))
+        if comm is not None and comm.size > 1:
+            if not builtin:
+                raise NotImplementedError(
+                    "ReplaceUnassignedPositions with a replacement function of the caller's is not available on frame "
+                    "shards: a run of unassigned frames that crosses the end of a shard would be handed over in pieces")
+            ends = comm.allgather(np.stack(ctx.label_ends()))               # [size, 2, n_mobile]
+            before_in, after_in = shard_halo(ends[:, 0], ends[:, 1], comm.rank, ctx.ENDS_NONE)
+        if fn is ReplaceUnassignedPositions.replace_with_last_known:
+            out = ctx.replace_unassigned(0, before_in, after_in)
+        elif fn is ReplaceUnassignedPositions.replace_with_next_known:
+            out = ctx.replace_unassigned(1, before_in, after_in)
+        elif isinstance(fn, _ReplaceWithCloser):
+            if st.real_trajectory is None:
+                raise ValueError("replace_with_closer needs a SiteTrajectory with a real trajectory (set_real_traj)")
+            records, n_positions = ctx.unknown_runs(before_in, after_in)
+            dec = records[records[:, 5] >= 0]
+            lens = dec[:, 2] - dec[:, 1]
+            # frame and atom of every position to decide, in record order: one gather, n_positions x 3
+            within = np.arange(n_positions) - np.repeat(dec[:, 5], lens)
+            frames = np.repeat(dec[:, 1] - ctx.frame0, lens) + within
+            atoms = np.repeat(np.where(sn.mobile_mask)[0][dec[:, 0]], lens)
+            positions = np.asarray(st.real_trajectory[frames, atoms], dtype=np.float64).reshape(-1, 3)
+            centers = sn.centers if sn.n_sites > 0 else np.zeros((0, 3))
+            out = ctx.replace_closer(records, centers, positions)
+        else:
+            records, _ = ctx.unknown_runs()
+            out = st._traj.copy()
+            for mob, start, end, before, after, _ in records:
+                start, end = start - ctx.frame0, end - ctx.frame0          # frames of `st`, as the reference passes them
+                out[start:end, mob] = fn(st, mob, before, start, after, end)        # :107-112
+        # :114-117 (see the class docstring for what the reference's copy keeps)
+        new_sn = sn.copy(with_computed=False)
+        new_sn.clear_attributes()
+        new = type(st)(new_sn, out, confidences=st._confs, _adopt=True)
+        if st._real_traj is not None:
+            new.set_real_traj(st._real_traj)
+        return new

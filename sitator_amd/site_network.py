@@ -76,7 +76,8 @@ class SiteNetwork(object):
 
     @staticmethod
     def _no_sites(centers=None):
-        return {"centers": centers, "vertices": None, "types": None, "named": {}}
+        # "computed": per named array, whether it was derived from a SiteTrajectory (SiteNetwork.py:26-29)
+        return {"centers": centers, "vertices": None, "types": None, "named": {}, "computed": {}}
 
     # -- named per-site / per-edge arrays -------------------------------------------------------------------------
     def _names_of(self, kind):
@@ -96,11 +97,19 @@ class SiteNetwork(object):
     def remove_attribute(self, attr):
         if self._sites["named"].pop(attr, None) is None:
             raise AttributeError("This SiteNetwork has no site or edge attribute `%s`" % attr)
+        self._sites["computed"].pop(attr, None)
 
     def clear_attributes(self):
         self._sites["named"] = {}
+        self._sites["computed"] = {}
 
-    def _store(self, kind, name, array):
+    def clear_computed_attributes(self):
+        """Removes the named arrays marked "computed": those derived from a ``SiteTrajectory``, which a changed
+        trajectory invalidates (``SiteNetwork.py:296-300``)."""
+        for name in [n for n, computed in self._sites["computed"].items() if computed]:
+            self.remove_attribute(name)
+
+    def _store(self, kind, name, array, computed=True):
         if self.ATTR_NAME_REGEX.match(name) is None:
             raise ValueError("Attribute name `%s` invalid; must begin with a letter and contain only letters, numbers, and underscores." % name)
         taken = name in self.__dict__ or hasattr(type(self), name) or self.has_attribute(name)
@@ -113,12 +122,13 @@ class SiteNetwork(object):
         if kind == self._EDGE and array.shape != (n, n):
             raise ValueError("Attribute matrix has shape %s; need first two dimensions to be %s" % (array.shape, (n, n)))
         self._sites["named"][name] = (kind, array)
+        self._sites["computed"][name] = bool(computed)
 
     def add_site_attribute(self, name, attr, computed=True):
-        self._store(self._SITE, name, attr)
+        self._store(self._SITE, name, attr, computed)
 
     def add_edge_attribute(self, name, attr, computed=True):
-        self._store(self._EDGE, name, attr)
+        self._store(self._EDGE, name, attr, computed)
 
     def __getattr__(self, attrkey):
         # only reached for names that are not ordinary attributes: the named arrays
@@ -204,7 +214,7 @@ class SiteNetwork(object):
         if rec["types"] is not None:
             part.site_types = rec["types"][pick]
         for name, (kind, array) in rec["named"].items():
-            part._store(kind, name, array[pick] if kind == self._SITE else array[pick][:, pick])
+            part._store(kind, name, array[pick] if kind == self._SITE else array[pick][:, pick], rec["computed"][name])
         return part
 
     def of_type(self, stype):
@@ -244,7 +254,8 @@ class SiteNetwork(object):
             raise ValueError("This SiteNetwork has no edge attributes")
         return {name: self._sites["named"][name][1][edge] for name in names}
 
-    def copy(self):
+    def copy(self, with_computed=True):
+        """A copy; ``with_computed=False`` leaves out the named arrays marked "computed" (``SiteNetwork.py:78-92``)."""
         twin = SiteNetwork(self.structure, self.static_mask, self.mobile_mask)
         rec = self._sites
         if rec["centers"] is not None:
@@ -254,5 +265,6 @@ class SiteNetwork(object):
             if rec["types"] is not None:
                 twin.site_types = rec["types"].copy()
             for name, (kind, array) in rec["named"].items():
-                twin._store(kind, name, array.copy())
+                if with_computed or not rec["computed"][name]:
+                    twin._store(kind, name, array.copy(), rec["computed"][name])
         return twin

@@ -120,9 +120,11 @@ class SiteTrajectory(object):
     def real_trajectory(self):
         return self._real_traj
 
-    def copy(self):
+    def copy(self, with_computed=True):
+        """A copy; ``with_computed=False``: without the network's arrays marked "computed" (``SiteNetwork.copy``)."""
         st = self[:]
-        st._sn = st._sn.copy()           # (not through the setter: the same sites, the labels need no second look)
+        # (not through the setter: the same sites, the labels need no second look)
+        st._sn = st._sn.copy(with_computed=with_computed)
         return st
 
     def set_real_traj(self, real_traj):
