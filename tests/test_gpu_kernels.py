@@ -1,6 +1,7 @@
 """GPU tests of kernel-level invariants through the C-ABI: both fill kernel generations give
 bit-identical rows, the fused assignment equals fill + predict, frames beyond the sampled
-displacement bound take the loose-table path and still match the oracle, empty inputs."""
+displacement bound take the loose-table path and still match the oracle, empty inputs.
+(Dynamic lattice mapping with maps that are not the identity: tests/test_gpu_dynamic_mapping.py.)"""
 import os
 
 import numpy as np
