@@ -328,6 +328,21 @@ int sit_recenter(sit_ctx *ctx, double *arr, int64_t F, int64_t A, const double *
  * the recentring as a pre-pass of the landmark analysis without a PCIe round trip of the trajectory.      */
 int sit_recenter_resident(sit_ctx *ctx, const double *masses, const double *factors, const double *add3);
 
+/* AverageVibrationalFrequency (dynamics/AverageVibrationalFrequency.py:30-61): per selected atom the speeds
+ * s[t] = |x[t+1] - x[t]| (t < n = F - 1, no periodic wrap), their spectrum X = rfft(s) (n / 2 + 1 bins; an exact-length
+ * transform by Bluestein's chirp-z over power-of-two passes in float64) and, over the bins with fmask != 0,
+ * band_power = sum |X_k|^2 and avg = sum freqs_k |X_k|^2 / band_power (0 / 0 = NaN where an atom never moves).
+ * positions: host [F, n_sel, 3], or NULL for the frames resident after sit_set_frames, of which `atoms` [n_sel] names the
+ * columns (F must then be the context's).  freqs / fmask [n / 2 + 1]: numpy's rfftfreq(n) and the band, made by the
+ * caller.  workspace_bytes: cap on the device buffers of a batch of atoms (0: SITATOR_SPECTRUM_WORKSPACE_MB, default
+ * 1024); atoms are processed in batches that fit, every atom's transform on its own: its results do not depend on the
+ * batch or on the other atoms.  spectrum [n_sel, n / 2 + 1, 2] and speeds [n_sel, n] are optional (NULL).  Reads only:
+ * frames, rows, labels and their validity stay as they are.  SIT_ERR_INVALID: F < 2, F - 1 > 2^29, an atom outside
+ * [0, A), F other than the resident frames', a cap below one atom's transform.                              */
+int sit_speed_spectrum(sit_ctx *ctx, const double *positions, int64_t F, const int64_t *atoms, int64_t n_sel,
+                       const double *freqs, const uint8_t *fmask, int64_t workspace_bytes, double *avg,
+                       double *band_power, double *spectrum, double *speeds);
+
 /* ---- frame sharding across GPUs ------------------------------------ */
 
 /* The reference has no communication layer (it is single-process); these are the exchange steps a frame-sharded

@@ -100,6 +100,7 @@ SIGNATURES = {
     "sit_running_mode": (C.c_int, [_vp, i64, i64, i64, C.c_int, _ip, i64, _ip]),
     "sit_recenter_resident": (C.c_int, [_vp, _dp, _dp, _dp]),
     "sit_recenter": (C.c_int, [_vp, _dp, i64, i64, _dp, _dp, _dp]),
+    "sit_speed_spectrum": (C.c_int, [_vp, _dp, i64, _ip, i64, _dp, _u8p, i64, _dp, _dp, _dp, _dp]),
     "sit_comm_unique_id": (C.c_int, [_u8p]),
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
     "sit_comm_destroy": (C.c_int, [_vp]),
@@ -696,6 +697,36 @@ class HipContext(object):
         assert len(masses) == self.A and len(factors) == self.A
         a3 = None if add3 is None else _f64(add3)
         self._check(self.lib.sit_recenter_resident(self._h, _d(masses), _d(factors), None if a3 is None else _d(a3)))
+
+    # -- AverageVibrationalFrequency: reads frames only (labels_version, rows and labels stay)
+    def speed_spectrum(self, freqs, fmask, positions=None, atoms=None, workspace_bytes=0, spectrum=False, speeds=False):
+        """Per selected atom ``(avg, band_power, spectrum, speeds)`` of the speeds ``|x[t+1] - x[t]|`` (``sit_speed_spectrum``):
+        the power-weighted mean of ``freqs`` over the bins where ``fmask`` holds, the power in them, and - where asked for,
+        else ``None`` - the complex bins ``[n_sel, n // 2 + 1]`` of ``rfft(speeds)`` and the speeds ``[n_sel, n]``,
+        ``n = F - 1``.  ``positions``: a host ``[F, n_sel, 3]`` float64 array; without it ``atoms`` names columns of the
+        frames resident after ``set_frames``.  ``workspace_bytes``: cap on the device buffers of a batch of atoms (0: the
+        default of 1 GiB)."""
+        if positions is not None:
+            positions = _f64(positions)
+            assert positions.ndim == 3 and positions.shape[2] == 3
+            F, n_sel = positions.shape[0], positions.shape[1]
+            idx = None
+        else:
+            idx = _i64(atoms).reshape(-1)
+            F, n_sel = self.F, len(idx)
+        nbins = max(F - 1, 0) // 2 + 1
+        freqs = _f64(freqs)
+        fmask = np.ascontiguousarray(fmask, dtype=np.uint8)
+        assert freqs.shape == (nbins,) and fmask.shape == (nbins,)
+        avg = np.empty(n_sel)
+        power = np.empty(n_sel)
+        spec = np.empty((n_sel, nbins), dtype=np.complex128) if spectrum else None
+        spd = np.empty((n_sel, max(F - 1, 0))) if speeds else None
+        self._check(self.lib.sit_speed_spectrum(
+            self._h, None if positions is None else _d(positions), int(F), None if idx is None else _i(idx), int(n_sel),
+            _d(freqs), fmask.ctypes.data_as(_u8p), int(workspace_bytes), _d(avg), _d(power),
+            None if spec is None else spec.ctypes.data_as(_dp), None if spd is None else _d(spd)))
+        return avg, power, spec, spd
 
     # ---- RCCL exchange of the frame-sharded path (csrc/comm.hip) ----
     def comm_create(self, unique_id, rank, world):

@@ -244,6 +244,7 @@ extern "C" void sit_destroy(sit_ctx *c)
                     c->d_fit_nrm2, c->d_fit_counts, c->d_fit_K, c->d_err, c->d_scratch};
     for (void *p : ptrs) if (p) sit_dfree(c, p);
     fitfast_free(c);
+    spectrum_free(c);
     fill_ring_free(c);
     stream_give(c->device, 1, c->copy_stream);
     stream_give(c->device, 2, c->copy_stream2);

@@ -150,6 +150,7 @@ struct sit_ctx {
     void *d_scratch = nullptr;
     i64 scratch_bytes = 0;
     void *fill_ring = nullptr;        // results of deferred fills not yet collected (fill.hip)
+    void *spectrum = nullptr;         // tables and buffers of sit_speed_spectrum (spectrum.hip); opaque here
 };
 
 #define HIP_TRY(ctx, expr)                                                              \
@@ -474,6 +475,7 @@ int sit_predict_internal(sit_ctx *c, double threshold, bool words_reset = false)
 int predict_reset_with_fill(sit_ctx *c, bool *done);                // cluster.hip: the fill's and the assignment's words in one launch
 int sit_label_counts(sit_ctx *c, bool zero = true);              // zero = false: the counts were reset by the caller
 void fitfast_free(sit_ctx *c);
+void spectrum_free(sit_ctx *c);
 bool fitfast_valid(sit_ctx *c);
 void fitfast_invalidate(sit_ctx *c);
 int fitfast_set_state(sit_ctx *c, const double *cen, const i64 *cnt, i64 K);

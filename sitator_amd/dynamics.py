@@ -11,13 +11,16 @@ device-resident site assignments:
   the device labels)
 * ``ReplaceUnassignedPositions``  (reference ``sitator/dynamics/ReplaceUnassignedPositions.py:26-117``; the nearest known
   label before and after every unassigned frame comes from a two-directional scan of the device labels)
+* ``AverageVibrationalFrequency``  (reference ``sitator/dynamics/AverageVibrationalFrequency.py:30-61``; speeds, their
+  exact-length Fourier transform and the band average per atom on the device, also straight from the trajectory a
+  ``LandmarkAnalysis`` left resident)
 """
 import logging
 import operator
 
 import numpy as np
 
-from . import errors
+from . import _lib, errors
 
 from .markov import markov_clustering
 from .merging import MergeSites
@@ -463,3 +466,94 @@ class ReplaceUnassignedPositions(object):
         if st._real_traj is not None:
             new.set_real_traj(st._real_traj)
         return new
+
+
+class AverageVibrationalFrequency(object):
+    """Average vibrational frequency of chosen atoms of a trajectory: the power spectrum of each atom's speed
+    ``|x[t+1] - x[t]|`` gives a power-weighted mean frequency over ``min_frequency < f < max_frequency`` (units of
+    1 / timestep; ``f = 0`` is always left out), and the result is the mean over the atoms (reference
+    ``dynamics/AverageVibrationalFrequency.py``, after de Klerk, van der Maas and Wagemaker, ACS Appl. Energy Mater. 1
+    (2018) 3230).  Its inverse is the mean vibrational period in frames: the threshold ``SmoothSiteTrajectory.run`` and
+    ``assign_to_last_known_site`` are usually given.
+
+    The speeds, the transform and the sums over the band are computed by HIP kernels (``sit_speed_spectrum``): the
+    transform has the exact length ``n_frames - 1`` (Bluestein's algorithm in float64), every atom has its own, and the
+    mean and standard deviation over the atoms are numpy's, on the host.
+
+    Deviation from the reference: trajectories are float64 only.  The reference would compute the speeds of a float32
+    trajectory in float32; here any other dtype raises the ``ValueError`` ``LandmarkAnalysis.run`` raises for its frames."""
+
+    def __init__(self, min_frequency=0, max_frequency=np.inf):
+        assert min_frequency >= 0                                  # the zero frequency is always excluded (:25-26)
+        self.min_frequency = min_frequency
+        self.max_frequency = max_frequency
+
+    def _band(self, n_frames):
+        if n_frames < 2:
+            raise ValueError("A trajectory of %d frames has no speeds" % n_frames)
+        freqs = np.fft.rfftfreq(n_frames - 1)                      # :43-45
+        fmask = (freqs > self.min_frequency) & (freqs < self.max_frequency)
+        assert np.any(fmask), "Trajectory too short?"
+        return freqs, fmask
+
+    @staticmethod
+    def _over_atoms(avg_freqs, band_power, return_stdev):
+        if np.any(band_power == 0.0):                              # np.average(freqs, weights = all zeros), :54
+            raise ZeroDivisionError("Weights sum to zero, can't be normalized")
+        avg_freq = np.mean(avg_freqs)                              # :56-61
+        if return_stdev:
+            return avg_freq, np.std(avg_freqs)
+        return avg_freq
+
+    def compute_avg_vibrational_freq(self, traj, mask, return_stdev=False):
+        """``traj``: a host trajectory ``[n_frames, n_atoms, 3]``, float64, not modified; ``mask``: the atoms to average
+        over, a boolean mask or an index array (whatever ``traj[:, mask]`` takes).  Returns the frequency, with
+        ``return_stdev`` ``(frequency, standard deviation over the atoms)``.
+
+        Raises ``AssertionError("Trajectory too short?")`` when no frequency lies in the band (always with two frames),
+        ``ValueError`` for fewer than two frames or another dtype, ``ZeroDivisionError`` when a chosen atom never
+        moves (its band holds no power)."""
+        traj = np.asarray(traj)
+        if traj.ndim != 3 or traj.shape[2] != 3:
+            raise ValueError("Wrong shape %s for traj." % (traj.shape,))
+        if traj.dtype != np.float64:
+            raise ValueError("Buffer dtype mismatch, expected 'double' but got '%s'" % traj.dtype)
+        freqs, fmask = self._band(traj.shape[0])
+        selected = np.ascontiguousarray(traj[:, mask])             # a copy: the caller's array stays as it is
+        if selected.ndim != 3:
+            raise ValueError("`mask` must select along the atoms")
+        if selected.shape[1] == 0:
+            return self._over_atoms(np.empty(0), np.empty(0), return_stdev)
+        ctx = _lib.HipContext(np.eye(3))                           # no cell enters: the differences are not wrapped
+        try:
+            avg_freqs, band_power, _, _ = ctx.speed_spectrum(freqs, fmask, positions=selected)
+        finally:
+            ctx.close()
+        return self._over_atoms(avg_freqs, band_power, return_stdev)
+
+    def compute_for_analysis(self, la, mask=None, return_stdev=False):
+        """The same from the trajectory a ``LandmarkAnalysis`` that has run left on its GPU: no upload, no gather on
+        the host.  ``mask``: boolean mask or index array over the atoms of a frame; ``None``: the mobile atoms of the run.
+
+        The frames are those ``run()`` received, as they were at that time: what the caller did to the array afterwards
+        is not seen.  Raises ``ValueError`` if the analysis recentred the frames on the device (``recenter_masses``: a
+        shift per frame changes the differences between frames, these are not the caller's frames any more) and
+        ``NotImplementedError`` after a run over frame shards (``comm`` of more than one rank, ``devices=[...]`` of more
+        than one GPU): a spectrum does not split over the frames."""
+        la._need_run()
+        if getattr(la, "_children", None) is not None or la._comm.size > 1 or la._ctx is None:
+            raise NotImplementedError("AverageVibrationalFrequency needs all frames of the trajectory on one GPU; "
+                                      "this analysis ran over frame shards")
+        if la._recenter_masses is not None:
+            raise ValueError("The analysis recentred its frames on the device (recenter_masses): they are not the "
+                             "trajectory run() was given; use compute_avg_vibrational_freq on that")
+        ctx = la._ctx
+        freqs, fmask = self._band(ctx.F)
+        if mask is None:
+            atoms = np.asarray(la._mobile_idx, dtype=np.int64)
+        else:
+            atoms = np.arange(ctx.A, dtype=np.int64)[mask]         # numpy's rules: length, negative indices, bounds
+        if len(atoms) == 0:
+            return self._over_atoms(np.empty(0), np.empty(0), return_stdev)
+        avg_freqs, band_power, _, _ = ctx.speed_spectrum(freqs, fmask, atoms=atoms)
+        return self._over_atoms(avg_freqs, band_power, return_stdev)

@@ -177,6 +177,7 @@ class LandmarkAnalysis(object):
             frame0 = int(np.sum(counts[:comm.rank]))
         static_idx = np.where(sn.static_mask)[0]
         mobile_idx = np.where(sn.mobile_mask)[0]
+        self._mobile_idx = mobile_idx          # the mobile columns of the resident frames (AverageVibrationalFrequency)
         prefit = None
         self._pipelined = False
         if hasattr(ctx, "prefault_assignments") and os.environ.get("SITATOR_PREFAULT", "1") != "0":

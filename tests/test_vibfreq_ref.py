@@ -1,0 +1,164 @@
+"""CPU-only: (1) the numpy restatement of AverageVibrationalFrequency (tests/vibfreq_ref.py) reproduces what the
+reference's own class returned (tests/golden/vibfreq_known_answers.npz); the GPU tests then compare the device path
+with the restatement's intermediates.  (2) The launch planner of the spectrum kernels (sitator_amd/csrc/spectrum_plan.h)
+compiled with the host compiler, as test_fill3_plan.py compiles fill3_plan.h."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import vibfreq_ref as V
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+VG = V.VibGoldens()
+LDS_LIMIT = 160 * 1024 - 256
+GIB = 1 << 30
+
+
+def test_golden_covers_the_cases_it_should():
+    kw = [VG.case(n)[2] for n in VG.names]
+    ns = [len(VG.case(n)[0]) - 1 for n in VG.names]
+    assert any(k["min_frequency"] == 0 and k["max_frequency"] == np.inf for k in kw)
+    assert any(k["min_frequency"] == 0.05 and k["max_frequency"] == 0.3 for k in kw)
+    assert any(k["return_stdev"] for k in kw) and any(not k["return_stdev"] for k in kw)
+    assert any(n % 2 for n in ns) and any(n % 2 == 0 for n in ns)
+    masks = [VG.case(n)[1] for n in VG.names]
+    assert any(m.dtype == np.bool_ and not m.all() for m in masks) and any(m.dtype != np.bool_ for m in masks)
+
+
+@pytest.mark.parametrize("name", VG.names)
+def test_restatement_reproduces_the_reference(name):
+    traj, mask, kw, expected = VG.case(name)
+    r = V.restatement(traj, mask, kw["min_frequency"], kw["max_frequency"])
+    got = np.array([r["mean"], r["std"]]) if kw["return_stdev"] else np.array([r["mean"]])
+    np.testing.assert_allclose(got, expected, rtol=1e-13, atol=0)
+
+
+def test_restatement_does_not_touch_its_input():
+    traj, mask, kw, _ = VG.case(VG.names[0])
+    before = traj.copy()
+    V.restatement(traj, mask)
+    assert np.array_equal(traj, before)
+
+
+# ---- the planner ----------------------------------------------------------------------------------------------------
+
+# One case per input line: n n_sel workspace_bytes want_spectrum; one output line: the plan.
+PROBE = r"""
+#include <stdio.h>
+#include "spectrum_plan.h"
+int main()
+{
+    long long n, n_sel, ws; int spec;
+    while (scanf("%lld %lld %lld %d", &n, &n_sel, &ws, &spec) == 4) {
+        SpPlanIn in; in.n = n; in.n_sel = n_sel; in.workspace_bytes = ws; in.want_spectrum = spec != 0;
+        const SpPlan p = sp_plan(in, sp_knobs_from_env());
+        if (p.err) { printf("error: %s\n", p.err); continue; }
+        printf("M %lld nbins %lld npass %d atom_bytes %lld batch %lld n_batches %lld workspace %lld passes",
+               (long long)p.M, (long long)p.nbins, p.npass, (long long)p.atom_bytes, (long long)p.atoms_per_batch,
+               (long long)p.n_batches, (long long)p.workspace);
+        for (int i = 0; i < p.npass; i++)
+            printf(" %d:%lld:%lld:%d:%d:%lld:%zu", p.pass[i].bits, (long long)p.pass[i].L, (long long)p.pass[i].S, p.pass[i].lines,
+                   p.pass[i].pad, (long long)p.pass[i].tiles, p.pass[i].lds);
+        printf("\n");
+    }
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    td = tmp_path_factory.mktemp("spectrum_plan")
+    src = td / "probe.cpp"
+    src.write_text(PROBE)
+    exe = str(td / "probe")
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "sitator_amd", "csrc"), str(src), "-o", exe])
+
+    def run(cases, env=None):
+        text = "".join("%d %d %d %d\n" % c for c in cases)
+        e = {k: v for k, v in os.environ.items() if not k.startswith("SITATOR_SPECTRUM_")}
+        e.update(env or {})
+        out = subprocess.check_output([exe], input=text.encode(), env=e).decode().splitlines()
+        assert len(out) == len(cases)
+        return [parse(line) for line in out]
+    return run
+
+
+def parse(line):
+    if line.startswith("error:"):
+        return {"err": line[7:]}
+    tok = line.split()
+    p = {tok[i]: int(tok[i + 1]) for i in range(0, 14, 2)}
+    p["passes"] = [dict(zip(("bits", "L", "S", "lines", "pad", "tiles", "lds"), (int(v) for v in t.split(":")))) for t in tok[15:]]
+    p["err"] = None
+    return p
+
+
+def check_consistent(p, n, n_sel, cap):
+    """What every plan must satisfy, whatever its numbers."""
+    assert p["err"] is None
+    M = p["M"]
+    assert M & (M - 1) == 0 and M >= 2 * n - 1 and (M // 2 < 2 * n - 1 or M == 2)      # the smallest power of two
+    assert p["nbins"] == n // 2 + 1
+    assert len(p["passes"]) == p["npass"]
+    S = M
+    for q in p["passes"]:
+        assert 1 <= q["bits"] <= 10 and q["L"] == 1 << q["bits"]
+        S //= q["L"]
+        assert q["S"] == S
+        assert q["lines"] >= 1 and q["lines"] * q["tiles"] * q["L"] == M               # whole workgroups cover every line
+        assert q["lds"] <= LDS_LIMIT
+        # re, im of every line (with its pad), the twiddles of the line, two doubles per thread
+        assert q["lds"] >= 8 * (2 * q["lines"] * (q["L"] + q["pad"]) + q["L"] + 2 * 256) - 8
+    assert S == 1
+    assert p["workspace"] == p["batch"] * p["atom_bytes"] <= cap
+    assert p["atom_bytes"] >= M * 16 + n * 8
+    assert p["batch"] >= 1 and p["n_batches"] == -(-n_sel // p["batch"])
+    assert (p["n_batches"] - 1) * p["batch"] < n_sel <= p["n_batches"] * p["batch"]
+
+
+@pytest.mark.parametrize("n,M,npass", [(2, 4, 1), (3, 8, 1), (512, 1024, 1), (513, 2048, 2), (99999, 1 << 18, 2),
+                                       (249999, 1 << 19, 2), (524288, 1 << 20, 2), (524289, 1 << 21, 3), (1 << 29, 1 << 30, 3)])
+def test_plan_lengths_and_passes(probe, n, M, npass):
+    cap = GIB if n < 1 << 25 else 1 << 36              # the longest transform is 16 GiB an atom: over the default cap
+    if cap > GIB:
+        assert "cap" in probe([(n, 3, 0, 1)])[0]["err"]
+    p, = probe([(n, 3, 0 if cap == GIB else cap, 1)])
+    check_consistent(p, n, 3, cap)
+    assert (p["M"], p["npass"]) == (M, npass)
+    if n <= 249999:
+        assert p["n_batches"] == 1                     # three atoms fit the default workspace at every tested length
+
+
+def test_plan_batches_under_the_cap(probe):
+    # C2 and C3 under the default cap, and caps that force batches of one and of two with a ragged last batch
+    c2, c3 = probe([(99999, 64, 0, 0), (249999, 448, 0, 0)])
+    check_consistent(c2, 99999, 64, GIB)
+    check_consistent(c3, 249999, 448, GIB)
+    assert c2["n_batches"] == 1 and c2["batch"] == 64
+    assert c3["n_batches"] == -(-448 // c3["batch"]) and c3["n_batches"] > 1          # 448 x 8 MiB does not fit 1 GiB
+    one, = probe([(257, 5, 0, 1)])
+    ab = one["atom_bytes"]
+    for cap, batch, nb in [(ab, 1, 5), (2 * ab, 2, 3), (2 * ab + ab - 1, 2, 3), (5 * ab, 5, 1), (99 * ab, 5, 1)]:
+        p, = probe([(257, 5, cap, 1)])
+        check_consistent(p, 257, 5, cap)
+        assert (p["batch"], p["n_batches"]) == (batch, nb)
+    p, = probe([(257, 5, ab - 1, 1)])
+    assert p["err"] and "cap" in p["err"]                                              # never more than the cap
+
+
+def test_plan_refuses_what_it_cannot_do(probe):
+    for n in (0, -1, (1 << 29) + 1):
+        p, = probe([(n, 1, 0, 0)])
+        assert p["err"]
+
+
+def test_plan_knobs_are_read_in_one_place(probe):
+    p, = probe([(700, 2, 0, 0)], env={"SITATOR_SPECTRUM_STAGE_BITS": "4"})
+    check_consistent(p, 700, 2, GIB)
+    assert p["npass"] == 3 and [q["bits"] for q in p["passes"]] == [3, 4, 4]
+    p, = probe([(99999, 64, 0, 0)], env={"SITATOR_SPECTRUM_WORKSPACE_MB": "64", "SITATOR_SPECTRUM_LINES": "4"})
+    check_consistent(p, 99999, 64, 64 << 20)
+    assert p["n_batches"] > 1 and all(q["lines"] <= 4 for q in p["passes"])
