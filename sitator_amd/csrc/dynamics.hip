@@ -1,92 +1,167 @@
 // The steps either side of the landmark path, on the device-resident label array:
+//   jump detection                           SiteTrajectory.py:307-373
 //   JumpAnalysis.run                         dynamics/JumpAnalysis.py:27-135
 //   SiteTrajectory.assign_to_last_known_site SiteTrajectory.py:235-304
 //   ReplaceUnassignedPositions.run           dynamics/ReplaceUnassignedPositions.py:90-117
 //   SmoothSiteTrajectory.running_windowed_mode   dynamics/SmoothSiteTrajectory.pyx:79-111
 //   RecenterTrajectory.run                   util/RecenterTrajectory.pyx:14-100
+// The first four are per-ion scans along the frames in chunks (the scheme, the summary and the state transitions:
+// label_scan.h): k_label_chunk_summary for all of them, then per scan a carry kernel and a replay kernel.
 #include <cmath>
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>
 
-#include <cstdio>
-
 #include "sit_internal.h"
+#include "label_scan.h"
+
+// The layout `lay(Carve &)` of an entry point's scratch: run once to size the buffer, once more to hand out its pieces
+template <class Lay>
+static int carve_scratch(sit_ctx *c, Lay lay)
+{
+    Carve cv = {nullptr, 0};
+    lay(cv);
+    const int rc = ensure_scratch(c, cv.used);
+    if (rc) return rc;
+    cv = {(char *)c->d_scratch, 0};
+    lay(cv);
+    return SIT_OK;
+}
+
+// Step (1) of every scan.  Grid (chunks, ceil(M / 64)).
+__global__ __launch_bounds__(64) void k_label_chunk_summary(const i64 *labels, i64 F, i64 M, int all_known, ChunkSummary *out)
+{
+    const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
+    if (j >= M) return;
+    out[c * M + j] = ls_summarise(labels + c * LS_CHUNK * M + j, M, ls_chunk_len(c, F), all_known != 0);
+}
+
+// ---- jump detection (SiteTrajectory.py:307-329) ----------------------------------------------------------
+// A forward fill of the last known site per ion; the replay reports the jumps as an [F, M] source array and/or as records.
+#define JUMP_NONE ((i64)0x8000000000000000ull)                   // sit_jump_sources: "no jump at this frame"
+
+__global__ void k_jump_chunk_carry(const i64 *labels, i64 F, i64 M, i64 nch, const i64 *last_in, const ChunkSummary *sum,
+                                   i64 *carry, i64 *last_out)
+{
+    const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= M) return;
+    i64 last = last_in ? last_in[j] : (F > 0 ? labels[j] : -1);       // last_known = traj[0] (:312)
+    for (i64 c = 0; c < nch; c++) {
+        carry[c * M + j] = last;
+        jump_advance(last, sum[c * M + j]);
+    }
+    last_out[j] = last;
+}
+
+// (Frame 0 of a context without carried-in state only defines the state: the carry starts from its label, no jump.)
+__global__ __launch_bounds__(64) void k_jump_emit(const i64 *labels, i64 F, i64 M, int unknown_as_jump, const i64 *carry,
+                                                  i64 *from, i64 *rec, u64 *counter, i64 max_rec)
+{
+    const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
+    if (j >= M) return;
+    const i64 f0 = c * LS_CHUNK, f1 = f0 + ls_chunk_len(c, F);
+    i64 last = carry[c * M + j];
+    for (i64 f = f0; f < f1; f++) {
+        const i64 cur = labels[f * M + j];
+        const i64 was = last;
+        const bool jumped = jump_step(last, cur, unknown_as_jump != 0);
+        if (from) from[f * M + j] = jumped ? was : JUMP_NONE;
+        if (rec && jumped) {
+            const u64 slot = atomicAdd(counter, 1ull);
+            if ((i64)slot < max_rec) { rec[4 * slot] = f; rec[4 * slot + 1] = j; rec[4 * slot + 2] = was; rec[4 * slot + 3] = cur; }
+        }
+    }
+}
+
+static int jump_scan(sit_ctx *c, int unknown_as_jump, const i64 *last_known_in, const ScanScratch<i64> &s, i64 *dfrom, i64 *drec,
+                     i64 max_rec, u64 *dcounter)
+{
+    const i64 M = c->M, F = c->F, nch = ls_chunks(F);
+    if (last_known_in) HIP_TRY(c, hipMemcpyAsync(s.in0, last_known_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+    if (dcounter) HIP_TRY(c, hipMemsetAsync(dcounter, 0, 8, c->stream));
+    const unsigned gy = (unsigned)((M + 63) / 64);
+    if (nch > 0) k_label_chunk_summary<<<dim3((unsigned)nch, gy), dim3(64), 0, c->stream>>>(c->d_labels, F, M, unknown_as_jump, s.sum);
+    k_jump_chunk_carry<<<dim3(gy), dim3(64), 0, c->stream>>>(c->d_labels, F, M, nch, last_known_in ? s.in0 : nullptr, s.sum,
+                                                            s.carry, s.out0);
+    if (nch > 0) k_jump_emit<<<dim3((unsigned)nch, gy), dim3(64), 0, c->stream>>>(c->d_labels, F, M, unknown_as_jump, s.carry,
+                                                                               dfrom, drec, dcounter, max_rec);
+    HIP_TRY(c, hipGetLastError());
+    return SIT_OK;
+}
+
+extern "C" int sit_jump_sources(sit_ctx *c, int unknown_as_jump, const i64 *last_known_in, i64 *from, i64 *last_known_out)
+{
+    if (!c || !from) return SIT_ERR_INVALID;
+    SIT_SETTLE(c);
+    SIT_REQUIRE(c, c->assign_valid, "sit_jump_sources: assignments needed");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const i64 N = c->N, M = c->M, nch = ls_chunks(c->F);
+    ScanScratch<i64> s;
+    i64 *dfrom;
+    int rc = carve_scratch(c, [&](Carve &cv) { s.lay(cv, M, nch); dfrom = cv.take<i64>(N); });
+    if (rc) return rc;
+    if ((rc = jump_scan(c, unknown_as_jump, last_known_in, s, dfrom, nullptr, 0, nullptr))) return rc;
+    if (N > 0) HIP_TRY(c, hipMemcpyAsync(from, dfrom, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+    if (last_known_out) HIP_TRY(c, hipMemcpyAsync(last_known_out, s.out0, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SIT_OK;
+}
+
+extern "C" int sit_jump_list(sit_ctx *c, int unknown_as_jump, const i64 *last_known_in, i64 max_records, i64 *records,
+                             i64 *n_records, i64 *last_known_out)
+{
+    if (!c || !n_records || (max_records > 0 && !records)) return SIT_ERR_INVALID;
+    SIT_SETTLE(c);
+    SIT_REQUIRE(c, c->assign_valid && max_records >= 0, "sit_jump_list: assignments needed");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const i64 M = c->M, nch = ls_chunks(c->F);
+    ScanScratch<i64> s;
+    i64 *drec;
+    u64 *dcount;
+    int rc = carve_scratch(c, [&](Carve &cv) { s.lay(cv, M, nch); drec = cv.take<i64>(4 * max_records); dcount = cv.take<u64>(1); });
+    if (rc) return rc;
+    if ((rc = jump_scan(c, unknown_as_jump, last_known_in, s, nullptr, drec, max_records, dcount))) return rc;
+    u64 n = 0;
+    HIP_TRY(c, hipMemcpyAsync(&n, dcount, 8, hipMemcpyDeviceToHost, c->stream));
+    if (last_known_out) HIP_TRY(c, hipMemcpyAsync(last_known_out, s.out0, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *n_records = (i64)n;
+    const i64 got = (i64)n < max_records ? (i64)n : max_records;
+    if (got > 0) {
+        HIP_TRY(c, hipMemcpyAsync(records, drec, (size_t)got * 32, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return SIT_OK;
+}
 
 // ---- JumpAnalysis --------------------------------------------------------------------------------------
 // Pass 1: the forward-filled state machine of JumpAnalysis.py:46-92 per ion, frames in order:
 //   jfrom = last_known, jto = frame value after re-assigning unassigned to last_known (or -1 when either is
 //   unknown), jtime = time_at_current if the ion jumped this frame else 0.
-// The state (last known site, time at it) is a scan over the frames.  Frames are cut into chunks of DCH:
-// (1) every (chunk, ion) summarises its chunk - first and last known label, the last frame where two consecutive
-// known labels INSIDE the chunk differ; (2) one lane per ion chains the summaries (a few hundred steps) into the
-// state at every chunk's start - whether the chunk's first known label is a jump depends on the carried-in site;
-// (3) every (chunk, ion) replays its chunk from that state.  (Was: one lane per ion walking all F frames.)
-#define DCH 256
-#define D_NONE ((i64)0x8000000000000000ull)
-
-__global__ __launch_bounds__(64) void k_ja_chunk_summary(const i64 *labels, i64 F, i64 M, i64 *first_known, i64 *last_known,
-                                                         i32 *first_pos, i32 *last_jump_pos)
-{
-    const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
-    if (j >= M) return;
-    const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
-    i64 fk = D_NONE, lk = D_NONE;
-    i32 fp = -1, ljp = -1;
-    for (i64 f = f0; f < f1; f++) {
-        const i64 cur = labels[f * M + j];
-        if (cur == -1) continue;
-        if (fk == D_NONE) { fk = cur; fp = (i32)(f - f0); }
-        else if (cur != lk && cur >= 0 && lk >= 0) ljp = (i32)(f - f0);   // :68,:74: both known
-        lk = cur;
-    }
-    first_known[c * M + j] = fk; last_known[c * M + j] = lk;
-    first_pos[c * M + j] = fp; last_jump_pos[c * M + j] = ljp;
-}
-
-// state at the start of every chunk: (last known site, time at current); the final state goes to last_out / tac_out
+// The state (last known site, time at it) at every chunk's start; the final state goes to last_out / tac_out.
 __global__ void k_ja_chunk_carry(const i64 *labels, i64 F, i64 M, i64 nch, const i64 *last_in, const i64 *tac_in,
-                                 const i64 *first_known, const i64 *last_known, const i32 *first_pos, const i32 *last_jump_pos,
-                                 i64 *carry_last, i64 *carry_tac, i64 *last_out, i64 *tac_out)
+                                 const ChunkSummary *sum, JaState *carry, i64 *last_out, i64 *tac_out)
 {
     const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= M) return;
-    i64 last, tac;
-    if (last_in) { last = last_in[j]; tac = tac_in[j]; }
-    else { last = F > 0 ? labels[j] : -1; tac = 1; }            // :46-49
+    JaState s = last_in ? JaState{last_in[j], tac_in[j]} : JaState{F > 0 ? labels[j] : -1, 1};   // :46-49
     for (i64 c = 0; c < nch; c++) {
-        carry_last[c * M + j] = last; carry_tac[c * M + j] = tac;
-        const i64 len = (c * DCH + DCH < F ? DCH : F - c * DCH);
-        const i64 fk = first_known[c * M + j];
-        i64 jp = last_jump_pos[c * M + j];
-        if (fk != D_NONE) {
-            if (last >= 0 && fk >= 0 && fk != last && jp < first_pos[c * M + j]) jp = first_pos[c * M + j];
-            last = last_known[c * M + j];
-        }
-        tac = jp >= 0 ? len - jp : tac + len;                    // :88-91: 1 after the jump frame, + 1 per frame
+        carry[c * M + j] = s;
+        ja_advance(s, sum[c * M + j], ls_chunk_len(c, F));
     }
-    last_out[j] = last; tac_out[j] = tac;
+    last_out[j] = s.last; tac_out[j] = s.tac;
 }
 
-__global__ __launch_bounds__(64) void k_ja_chunk_replay(const i64 *labels, i64 F, i64 M, const i64 *carry_last, const i64 *carry_tac,
+__global__ __launch_bounds__(64) void k_ja_chunk_replay(const i64 *labels, i64 F, i64 M, const JaState *carry,
                                                         i32 *jfrom, i32 *jto, i32 *jtime, u64 *n_problems)
 {
     const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
     u64 problems = 0;
     if (j < M) {
-        const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
-        i64 last = carry_last[c * M + j], tac = carry_tac[c * M + j];
+        const i64 f0 = c * LS_CHUNK, f1 = f0 + ls_chunk_len(c, F);
+        JaState s = carry[c * M + j];
         for (i64 f = f0; f < f1; f++) {
-            const i64 cur = labels[f * M + j];
-            const bool unassigned = cur == -1;
-            const i64 fr = unassigned ? last : cur;              // :65-67
-            const bool fknown = fr >= 0 && last >= 0;            // :68
-            if (!fknown) problems++;
-            const bool jumped = fknown && fr != last;            // :74
-            const i64 o = f * M + j;
-            jfrom[o] = fknown ? (i32)last : -1;
-            jto[o] = fknown ? (i32)fr : -1;
-            jtime[o] = jumped ? (i32)tac : 0;
-            tac = jumped ? 1 : tac + 1;                          // :88-91
-            if (!unassigned) last = cur;                         // :94
+            const JaStep o = ja_step(s, labels[f * M + j]);
+            jfrom[f * M + j] = o.from; jto[f * M + j] = o.to; jtime[f * M + j] = o.time;
+            problems += o.problem;
         }
     }
     for (int off = 32; off > 0; off >>= 1) problems += __shfl_down(problems, off);
@@ -133,42 +208,27 @@ extern "C" int sit_jump_analysis(sit_ctx *c, i64 K, const i64 *last_known_in, co
     SIT_REQUIRE(c, c->assign_valid && K > 0, "sit_jump_analysis: assignments needed");
     SIT_REQUIRE(c, (last_known_in == nullptr) == (time_at_current_in == nullptr), "sit_jump_analysis: halo arrays come in pairs");
     HIP_TRY(c, hipSetDevice(c->device));
-    const i64 N = c->N, M = c->M, F = c->F;
-    const i64 nch = (F + DCH - 1) / DCH;
-    const i64 bytes = N * 12 + 4 * M * 8 + K * K * 24 + K * 8 + 64 + nch * M * 40 + 64;
-    int rc = ensure_scratch(c, bytes + 1024);
+    const i64 N = c->N, M = c->M, F = c->F, nch = ls_chunks(F);
+    const i64 nacc = 3 * K * K + K + 2;      // n_ij, time sum, time n [K, K]; total time [K]; problems, largest out-of-range site index + 1
+    ScanScratch<JaState> s;
+    u64 *d_acc;
+    i32 *d_from, *d_to, *d_time;
+    int rc = carve_scratch(c, [&](Carve &cv) {
+        s.lay(cv, M, nch); d_acc = cv.take<u64>(nacc); d_from = cv.take<i32>(N); d_to = cv.take<i32>(N); d_time = cv.take<i32>(N);
+    });
     if (rc) return rc;
-    char *p = (char *)c->d_scratch;
-    double *d_nij = (double *)p; p += K * K * 8;
-    double *d_ts = (double *)p; p += K * K * 8;
-    u64 *d_tn = (u64 *)p; p += K * K * 8;
-    u64 *d_tt = (u64 *)p; p += K * 8;
-    u64 *d_np = (u64 *)p; p += 64;
-    i64 *d_lin = (i64 *)p; p += M * 8;
-    i64 *d_tin = (i64 *)p; p += M * 8;
-    i64 *d_lout = (i64 *)p; p += M * 8;
-    i64 *d_tout = (i64 *)p; p += M * 8;
-    i32 *d_from = (i32 *)p; p += N * 4;
-    i32 *d_to = (i32 *)p; p += N * 4;
-    i32 *d_time = (i32 *)p; p += N * 4;
-    p += (8 - ((size_t)p & 7)) & 7;
-    i64 *d_fk = (i64 *)p; p += nch * M * 8;
-    i64 *d_lk = (i64 *)p; p += nch * M * 8;
-    i64 *d_cl = (i64 *)p; p += nch * M * 8;
-    i64 *d_ct = (i64 *)p; p += nch * M * 8;
-    i32 *d_fp = (i32 *)p; p += nch * M * 4;
-    i32 *d_jp = (i32 *)p;
-    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, (size_t)(K * K * 24 + K * 8 + 64), c->stream));
+    double *d_nij = (double *)d_acc, *d_ts = d_nij + K * K;
+    u64 *d_tn = d_acc + 2 * K * K, *d_tt = d_tn + K * K, *d_np = d_tt + K;
+    HIP_TRY(c, hipMemsetAsync(d_acc, 0, (size_t)nacc * 8, c->stream));
     if (last_known_in) {
-        HIP_TRY(c, hipMemcpyAsync(d_lin, last_known_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d_tin, time_at_current_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(s.in0, last_known_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(s.in1, time_at_current_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
     }
     const dim3 cgrid((unsigned)(nch > 0 ? nch : 1), (unsigned)((M + 63) / 64));
-    if (nch > 0) k_ja_chunk_summary<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, d_fk, d_lk, d_fp, d_jp);
+    if (nch > 0) k_label_chunk_summary<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, 0, s.sum);
     k_ja_chunk_carry<<<dim3((unsigned)((M + 63) / 64)), dim3(64), 0, c->stream>>>(
-        c->d_labels, F, M, nch, last_known_in ? d_lin : nullptr, last_known_in ? d_tin : nullptr, d_fk, d_lk, d_fp, d_jp,
-        d_cl, d_ct, d_lout, d_tout);
-    if (nch > 0) k_ja_chunk_replay<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, d_cl, d_ct, d_from, d_to, d_time, d_np);
+        c->d_labels, F, M, nch, last_known_in ? s.in0 : nullptr, last_known_in ? s.in1 : nullptr, s.sum, s.carry, s.out0, s.out1);
+    if (nch > 0) k_ja_chunk_replay<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, s.carry, d_from, d_to, d_time, d_np);
     if (F > 0) k_ja_accumulate<<<dim3((unsigned)F), dim3(256), 0, c->stream>>>(d_from, d_to, d_time, F, M, K, d_nij, d_ts, d_tn, d_tt, d_np + 1);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipMemcpyAsync(n_ij, d_nij, (size_t)(K * K) * 8, hipMemcpyDeviceToHost, c->stream));
@@ -177,71 +237,42 @@ extern "C" int sit_jump_analysis(sit_ctx *c, i64 K, const i64 *last_known_in, co
     HIP_TRY(c, hipMemcpyAsync(total_time, d_tt, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
     u64 *h_np = (u64 *)c->h_pinned;                             // [0] problems, [1] largest out-of-range site index + 1
     HIP_TRY(c, hipMemcpyAsync(h_np, d_np, 16, hipMemcpyDeviceToHost, c->stream));
-    if (last_known_out) HIP_TRY(c, hipMemcpyAsync(last_known_out, d_lout, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
-    if (time_at_current_out) HIP_TRY(c, hipMemcpyAsync(time_at_current_out, d_tout, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    if (last_known_out) HIP_TRY(c, hipMemcpyAsync(last_known_out, s.out0, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    if (time_at_current_out) HIP_TRY(c, hipMemcpyAsync(time_at_current_out, s.out1, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *n_problems = (i64)h_np[0];
-    if (h_np[1]) {
-        char text[128];
-        snprintf(text, sizeof(text), "index %lld is out of bounds for axis 0 with size %lld", (long long)h_np[1] - 1, (long long)K);
-        c->msg = text;
-        return SIT_ERR_INVALID;
-    }
+    if (h_np[1]) return index_out_of_bounds(c, (i64)h_np[1] - 1, K);
     return SIT_OK;
 }
 
 // ---- assign_to_last_known_site (SiteTrajectory.py:235-304) -----------------------------------------------
 // Rewrites the device labels in place.  frame_max[f] = max over ions of the time an ion had been unknown when it
-// became known again at frame f (for the reference's max statistic).  The per-ion state (last known site, frames
-// unknown so far) is a scan over the frames, done in chunks like k_ja_chunk_*: summary (last known label of the
-// chunk, unknown frames after it), carry chain, replay.
-__global__ __launch_bounds__(64) void k_alk_chunk_summary(const i64 *labels, i64 F, i64 M, i64 *last_known, i32 *trailing)
-{
-    const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
-    if (j >= M) return;
-    const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
-    i64 lk = D_NONE;
-    i32 tr = 0;
-    for (i64 f = f0; f < f1; f++) {
-        const i64 cur = labels[f * M + j];
-        if (cur != -1) { lk = cur; tr = 0; } else tr++;
-    }
-    last_known[c * M + j] = lk; trailing[c * M + j] = tr;
-}
-
-__global__ void k_alk_chunk_carry(i64 F, i64 M, i64 nch, const i64 *last_in, const i64 *tu_in, const i64 *last_known,
-                                  const i32 *trailing, i64 *carry_last, i64 *carry_tu, i64 *last_out, i64 *tu_out)
+// became known again at frame f (for the reference's max statistic).
+__global__ void k_alk_chunk_carry(i64 F, i64 M, i64 nch, const i64 *last_in, const i64 *tu_in, const ChunkSummary *sum,
+                                  AlkState *carry, i64 *last_out, i64 *tu_out)
 {
     const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= M) return;
-    i64 last = last_in ? last_in[j] : -1, tu = tu_in ? tu_in[j] : 0;
+    AlkState s = {last_in ? last_in[j] : -1, tu_in ? tu_in[j] : 0};
     for (i64 c = 0; c < nch; c++) {
-        carry_last[c * M + j] = last; carry_tu[c * M + j] = tu;
-        const i64 lk = last_known[c * M + j];
-        if (lk != D_NONE) { last = lk; tu = trailing[c * M + j]; }
-        else tu += (c * DCH + DCH < F ? DCH : F - c * DCH);
+        carry[c * M + j] = s;
+        alk_advance(s, sum[c * M + j], ls_chunk_len(c, F));
     }
-    last_out[j] = last; tu_out[j] = tu;
+    last_out[j] = s.last; tu_out[j] = s.tu;
 }
 
-__global__ __launch_bounds__(64) void k_alk_chunk_replay(i64 *labels, i64 F, i64 M, i64 threshold, const i64 *carry_last,
-                                                         const i64 *carry_tu, i32 *frame_max, u64 *stats)
+__global__ __launch_bounds__(64) void k_alk_chunk_replay(i64 *labels, i64 F, i64 M, i64 threshold, const AlkState *carry,
+                                                         i32 *frame_max, u64 *stats)
 {
     const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
     u64 sum_t = 0, n_t = 0, reassigned = 0;
     if (j < M) {
-        const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
-        i64 last = carry_last[c * M + j], tu = carry_tu[c * M + j];
+        const i64 f0 = c * LS_CHUNK, f1 = f0 + ls_chunk_len(c, F);
+        AlkState s = carry[c * M + j];
         for (i64 f = f0; f < f1; f++) {
-            const i64 cur = labels[f * M + j];
-            if (cur != -1) {
-                last = cur;                                           // :261
-                if (tu != 0) { sum_t += (u64)tu; n_t++; atomicMax(&frame_max[f], (i32)tu); }   // :263-271
-                tu = 0;                                               // :273
-            } else {
-                if (tu < threshold) { labels[f * M + j] = last; reassigned++; }   // :275-278
-                tu++;                                                 // :279
-            }
+            const AlkStep o = alk_step(s, labels[f * M + j], threshold);
+            if (o.ended) { sum_t += (u64)o.ended; n_t++; atomicMax(&frame_max[f], (i32)o.ended); }   // :263-271
+            if (o.reassign) { labels[f * M + j] = s.last; reassigned++; }                            // :275-278
         }
     }
     for (int off = 32; off > 0; off >>= 1) {
@@ -261,85 +292,56 @@ extern "C" int sit_assign_last_known(sit_ctx *c, i64 frame_threshold, const i64 
     SIT_SETTLE(c);
     SIT_REQUIRE(c, c->assign_valid, "sit_assign_last_known: assignments needed");
     HIP_TRY(c, hipSetDevice(c->device));
-    const i64 M = c->M, F = c->F, N = c->N;
-    const i64 nch = (F + DCH - 1) / DCH;
-    int rc = ensure_scratch(c, 4 * M * 8 + F * 4 + 64 + 256 + nch * M * 28 + 64);
+    const i64 M = c->M, F = c->F, N = c->N, nch = ls_chunks(F);
+    const i64 nfm = F > 0 ? F : 1;
+    ScanScratch<AlkState> s;
+    u64 *d_st;
+    i32 *d_fm;
+    int rc = carve_scratch(c, [&](Carve &cv) { s.lay(cv, M, nch); d_st = cv.take<u64>(3); d_fm = cv.take<i32>(nfm); });
     if (rc) return rc;
-    char *p = (char *)c->d_scratch;
-    u64 *d_st = (u64 *)p; p += 64;
-    i64 *d_lk = (i64 *)p; p += nch * M * 8;
-    i64 *d_cl = (i64 *)p; p += nch * M * 8;
-    i64 *d_ct = (i64 *)p; p += nch * M * 8;
-    i64 *d_lin = (i64 *)p; p += M * 8;
-    i64 *d_tin = (i64 *)p; p += M * 8;
-    i64 *d_lout = (i64 *)p; p += M * 8;
-    i64 *d_tout = (i64 *)p; p += M * 8;
-    i32 *d_fm = (i32 *)p; p += (F > 0 ? F : 1) * 4;
-    i32 *d_tr = (i32 *)p;
-    HIP_TRY(c, hipMemsetAsync(d_st, 0, 64, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d_fm, 0, (size_t)(F > 0 ? F : 1) * 4, c->stream));
-    if (last_known_in) HIP_TRY(c, hipMemcpyAsync(d_lin, last_known_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
-    if (time_unknown_in) HIP_TRY(c, hipMemcpyAsync(d_tin, time_unknown_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_st, 0, 24, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_fm, 0, (size_t)nfm * 4, c->stream));
+    if (last_known_in) HIP_TRY(c, hipMemcpyAsync(s.in0, last_known_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+    if (time_unknown_in) HIP_TRY(c, hipMemcpyAsync(s.in1, time_unknown_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
     const dim3 cgrid((unsigned)(nch > 0 ? nch : 1), (unsigned)((M + 63) / 64));
-    if (nch > 0) k_alk_chunk_summary<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, d_lk, d_tr);
+    if (nch > 0) k_label_chunk_summary<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, 0, s.sum);
     k_alk_chunk_carry<<<dim3((unsigned)((M + 63) / 64)), dim3(64), 0, c->stream>>>(
-        F, M, nch, last_known_in ? d_lin : nullptr, time_unknown_in ? d_tin : nullptr, d_lk, d_tr, d_cl, d_ct, d_lout, d_tout);
-    if (nch > 0) k_alk_chunk_replay<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, frame_threshold, d_cl, d_ct, d_fm, d_st);
+        F, M, nch, last_known_in ? s.in0 : nullptr, time_unknown_in ? s.in1 : nullptr, s.sum, s.carry, s.out0, s.out1);
+    if (nch > 0) k_alk_chunk_replay<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, frame_threshold, s.carry, d_fm, d_st);
     HIP_TRY(c, hipGetLastError());
     u64 st[3];
     HIP_TRY(c, hipMemcpyAsync(st, d_st, 24, hipMemcpyDeviceToHost, c->stream));
     if (F > 0) HIP_TRY(c, hipMemcpyAsync(frame_max, d_fm, (size_t)F * 4, hipMemcpyDeviceToHost, c->stream));
     if (labels_out && N > 0) HIP_TRY(c, hipMemcpyAsync(labels_out, c->d_labels, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
-    if (last_known_out) HIP_TRY(c, hipMemcpyAsync(last_known_out, d_lout, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
-    if (time_unknown_out) HIP_TRY(c, hipMemcpyAsync(time_unknown_out, d_tout, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    if (last_known_out) HIP_TRY(c, hipMemcpyAsync(last_known_out, s.out0, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
+    if (time_unknown_out) HIP_TRY(c, hipMemcpyAsync(time_unknown_out, s.out1, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     stats3[0] = (i64)st[0]; stats3[1] = (i64)st[1]; stats3[2] = (i64)st[2];
     return SIT_OK;
 }
 
 // ---- ReplaceUnassignedPositions (dynamics/ReplaceUnassignedPositions.py:90-117) ---------------------------
-// Every unknown frame of an ion needs the nearest known label BEFORE it and the nearest AFTER it: the scan of k_alk_*
-// run in both directions.  (1) every (chunk, ion) summarises its chunk: first and last known label and where the first
-// one is; (2) one lane per ion chains the summaries forwards (`before` at every chunk's start) and backwards (`after`
-// at every chunk's end, and the frame it was found at: where a run that leaves the chunk ends); (3) every (chunk, ion)
-// replays its chunk.  The resident labels are only read.
-__global__ __launch_bounds__(64) void k_rup_chunk_summary(const i64 *labels, i64 F, i64 M, i64 *first_known, i64 *last_known,
-                                                          i32 *first_pos)
-{
-    const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
-    if (j >= M) return;
-    const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
-    i64 fk = D_NONE, lk = D_NONE;
-    i32 fp = -1;
-    for (i64 f = f0; f < f1; f++) {
-        const i64 cur = labels[f * M + j];
-        if (cur == -1) continue;
-        if (fp < 0) { fk = cur; fp = (i32)(f - f0); }
-        lk = cur;
-    }
-    first_known[c * M + j] = fk; last_known[c * M + j] = lk; first_pos[c * M + j] = fp;
-}
-
+// Every unknown frame of an ion needs the nearest known label BEFORE it and the nearest AFTER it: the carry chains the
+// summaries forwards and backwards.  The resident labels are only read.
 // carry_before[c]: the label a run that starts chunk c has before it; carry_after[c] / carry_end[c]: the label after a
 // run that reaches the end of chunk c and the (local) frame that label stands at (F: none).  ends[0..M) / ends[M..2M):
-// first and last known label of the ion in these frames (D_NONE: none) - without the values carried in.
-__global__ void k_rup_chunk_carry(i64 F, i64 M, i64 nch, const i64 *before_in, const i64 *after_in, const i64 *first_known,
-                                  const i64 *last_known, const i32 *first_pos, i64 *carry_before, i64 *carry_after,
-                                  i64 *carry_end, i64 *ends)
+// first and last known label of the ion in these frames (INT64_MIN: none) - without the values carried in.
+__global__ void k_rup_chunk_carry(i64 F, i64 M, i64 nch, const i64 *before_in, const i64 *after_in, const ChunkSummary *sum,
+                                  i64 *carry_before, i64 *carry_after, i64 *carry_end, i64 *ends)
 {
     const i64 j = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= M) return;
-    i64 before = before_in ? before_in[j] : -1, last = D_NONE;
+    i64 before = before_in ? before_in[j] : -1, after = after_in ? after_in[j] : -1, end = F;
+    i64 first = INT64_MIN, last = INT64_MIN;
     for (i64 c = 0; c < nch; c++) {
         carry_before[c * M + j] = before;
-        const i64 lk = last_known[c * M + j];
-        if (lk != D_NONE) before = last = lk;
+        jump_advance(before, sum[c * M + j]);
+        if (sum[c * M + j].first_pos >= 0) last = sum[c * M + j].last;
     }
-    i64 after = after_in ? after_in[j] : -1, end = F, first = D_NONE;
     for (i64 c = nch - 1; c >= 0; c--) {
         carry_after[c * M + j] = after; carry_end[c * M + j] = end;
-        const i32 fp = first_pos[c * M + j];
-        if (fp >= 0) { after = first = first_known[c * M + j]; end = c * DCH + fp; }
+        rup_back_advance(after, end, sum[c * M + j], c * LS_CHUNK);
+        if (sum[c * M + j].first_pos >= 0) first = sum[c * M + j].first;
     }
     ends[j] = first; ends[M + j] = last;
 }
@@ -350,21 +352,12 @@ __global__ __launch_bounds__(64) void k_rup_chunk_replay(const i64 *labels, i64 
 {
     const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
     if (j >= M) return;
-    const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
-    if (mode == 0) {
-        i64 fill = carry_before[c * M + j];
-        for (i64 f = f0; f < f1; f++) {
-            const i64 cur = labels[f * M + j];
-            if (cur != -1) fill = cur;
-            out[f * M + j] = fill;
-        }
-    } else {
-        i64 fill = carry_after[c * M + j];
-        for (i64 f = f1 - 1; f >= f0; f--) {
-            const i64 cur = labels[f * M + j];
-            if (cur != -1) fill = cur;
-            out[f * M + j] = fill;
-        }
+    const i64 f0 = c * LS_CHUNK, f1 = f0 + ls_chunk_len(c, F);
+    i64 fill = (mode == 0 ? carry_before : carry_after)[c * M + j];
+    for (i64 i = 0; i < f1 - f0; i++) {
+        const i64 f = mode == 0 ? f0 + i : f1 - 1 - i;
+        jump_step(fill, labels[f * M + j], false);
+        out[f * M + j] = fill;
     }
 }
 
@@ -378,7 +371,7 @@ __global__ __launch_bounds__(64) void k_rup_runs(const i64 *labels, i64 F, i64 M
 {
     const i64 c = blockIdx.x, j = (i64)blockIdx.y * 64 + threadIdx.x;
     if (j >= M) return;
-    const i64 f0 = c * DCH, f1 = f0 + DCH < F ? f0 + DCH : F;
+    const i64 f0 = c * LS_CHUNK, f1 = f0 + LS_CHUNK < F ? f0 + LS_CHUNK : F;
     i64 before = carry_before[c * M + j];
     i64 runs = EMIT ? n_runs[c * M + j] : 0, pos = EMIT ? n_pos[c * M + j] : 0;
     bool open = f0 > 0 && labels[(f0 - 1) * M + j] == -1;        // a run of an earlier chunk is still going
@@ -408,7 +401,7 @@ __global__ __launch_bounds__(64) void k_rup_runs(const i64 *labels, i64 F, i64 M
 }
 
 // Exclusive prefix sums of the two count tables in ION-MAJOR order (item i = j * nch + c lives at [c * M + j]): the
-// reference walks the ions, and the runs of an ion in frame order (:99-112).  One workgroup: the tables have F * M / DCH
+// reference walks the ions, and the runs of an ion in frame order (:99-112).  One workgroup: the tables have F * M / LS_CHUNK
 // entries.  totals[0], totals[1]: the sums.
 __global__ __launch_bounds__(1024) void k_rup_scan(i64 *n_runs, i64 *n_pos, i64 M, i64 nch, i64 *totals)
 {
@@ -435,39 +428,18 @@ __global__ __launch_bounds__(1024) void k_rup_scan(i64 *n_runs, i64 *n_pos, i64 
     if (threadIdx.x == 1023) { totals[0] = sr[1023]; totals[1] = sp[1023]; }
 }
 
-// scratch of the two-directional scan: the three launches every entry point below starts with
-struct RupScan {
-    i64 *before_in, *after_in, *fk, *lk, *cb, *ca, *ce, *ends;
-    i32 *fp;
-    char *rest;
-};
-
-static i64 rup_scan_bytes(i64 M, i64 nch) { return 4 * M * 8 + nch * M * 44 + 64; }
-
-static int rup_scan(sit_ctx *c, char *p, const i64 *before_in, const i64 *after_in, RupScan *s)
+// the two launches every entry point below starts with
+static int rup_scan(sit_ctx *c, const i64 *before_in, const i64 *after_in, const RupScratch &s)
 {
-    const i64 M = c->M, F = c->F, nch = (F + DCH - 1) / DCH;
-    s->before_in = (i64 *)p; p += M * 8;
-    s->after_in = (i64 *)p; p += M * 8;
-    s->ends = (i64 *)p; p += 2 * M * 8;
-    s->fk = (i64 *)p; p += nch * M * 8;
-    s->lk = (i64 *)p; p += nch * M * 8;
-    s->cb = (i64 *)p; p += nch * M * 8;
-    s->ca = (i64 *)p; p += nch * M * 8;
-    s->ce = (i64 *)p; p += nch * M * 8;
-    s->fp = (i32 *)p; p += nch * M * 4;
-    p += (8 - ((size_t)p & 7)) & 7;
-    s->rest = p;
-    if (M == 0) return SIT_OK;
+    const i64 M = c->M, F = c->F, nch = ls_chunks(F);
     if (before_in) {
-        HIP_TRY(c, hipMemcpyAsync(s->before_in, before_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(s->after_in, after_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(s.before_in, before_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(s.after_in, after_in, (size_t)M * 8, hipMemcpyHostToDevice, c->stream));
     }
     const unsigned gy = (unsigned)((M + 63) / 64);
-    if (nch > 0) k_rup_chunk_summary<<<dim3((unsigned)nch, gy), dim3(64), 0, c->stream>>>(c->d_labels, F, M, s->fk, s->lk, s->fp);
-    k_rup_chunk_carry<<<dim3(gy), dim3(64), 0, c->stream>>>(F, M, nch, before_in ? s->before_in : nullptr,
-                                                          before_in ? s->after_in : nullptr, s->fk, s->lk, s->fp, s->cb, s->ca,
-                                                          s->ce, s->ends);
+    if (nch > 0) k_label_chunk_summary<<<dim3((unsigned)nch, gy), dim3(64), 0, c->stream>>>(c->d_labels, F, M, 0, s.sum);
+    k_rup_chunk_carry<<<dim3(gy), dim3(64), 0, c->stream>>>(F, M, nch, before_in ? s.before_in : nullptr,
+                                                          before_in ? s.after_in : nullptr, s.sum, s.cb, s.ca, s.ce, s.ends);
     HIP_TRY(c, hipGetLastError());
     return SIT_OK;
 }
@@ -477,13 +449,13 @@ extern "C" int sit_label_ends(sit_ctx *c, i64 *first_known, i64 *last_known)
     if (!c || !first_known || !last_known) return SIT_ERR_INVALID;
     SIT_SETTLE(c);
     SIT_REQUIRE(c, c->assign_valid, "sit_label_ends: assignments needed");
-    const i64 M = c->M, nch = (c->F + DCH - 1) / DCH;
+    const i64 M = c->M, nch = ls_chunks(c->F);
     if (M == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, rup_scan_bytes(M, nch));
+    RupScratch s;
+    int rc = carve_scratch(c, [&](Carve &cv) { s.lay(cv, M, nch); });
     if (rc) return rc;
-    RupScan s;
-    if ((rc = rup_scan(c, (char *)c->d_scratch, nullptr, nullptr, &s))) return rc;
+    if ((rc = rup_scan(c, nullptr, nullptr, s))) return rc;
     HIP_TRY(c, hipMemcpyAsync(first_known, s.ends, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(last_known, s.ends + M, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -497,14 +469,14 @@ extern "C" int sit_replace_unassigned(sit_ctx *c, int mode, const i64 *before_in
     SIT_REQUIRE(c, c->assign_valid, "sit_replace_unassigned: assignments needed");
     SIT_REQUIRE(c, mode == 0 || mode == 1, "sit_replace_unassigned: mode is 0 (last known) or 1 (next known)");
     SIT_REQUIRE(c, (before_in == nullptr) == (after_in == nullptr), "sit_replace_unassigned: the carried-in arrays come in pairs");
-    const i64 M = c->M, F = c->F, N = c->N, nch = (F + DCH - 1) / DCH;
+    const i64 M = c->M, F = c->F, N = c->N, nch = ls_chunks(F);
     if (N == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, rup_scan_bytes(M, nch) + N * 8);
+    RupScratch s;
+    i64 *d_out;
+    int rc = carve_scratch(c, [&](Carve &cv) { s.lay(cv, M, nch); d_out = cv.take<i64>(N); });
     if (rc) return rc;
-    RupScan s;
-    if ((rc = rup_scan(c, (char *)c->d_scratch, before_in, after_in, &s))) return rc;
-    i64 *d_out = (i64 *)s.rest;
+    if ((rc = rup_scan(c, before_in, after_in, s))) return rc;
     k_rup_chunk_replay<<<dim3((unsigned)nch, (unsigned)((M + 63) / 64)), dim3(64), 0, c->stream>>>(c->d_labels, F, M, mode, s.cb,
                                                                                                  s.ca, d_out);
     HIP_TRY(c, hipGetLastError());
@@ -520,15 +492,18 @@ extern "C" int sit_unknown_runs(sit_ctx *c, const i64 *before_in, const i64 *aft
     SIT_SETTLE(c);
     SIT_REQUIRE(c, c->assign_valid && max_records >= 0, "sit_unknown_runs: assignments needed");
     SIT_REQUIRE(c, (before_in == nullptr) == (after_in == nullptr), "sit_unknown_runs: the carried-in arrays come in pairs");
-    const i64 M = c->M, F = c->F, nch = (F + DCH - 1) / DCH;
+    const i64 M = c->M, F = c->F, nch = ls_chunks(F);
     *n_records = 0; *n_positions = 0;
     if (c->N == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, rup_scan_bytes(M, nch) + 2 * nch * M * 8 + 16 + max_records * 48);
+    RupScratch s;
+    i64 *d_nr, *d_np, *d_tot, *d_rec;
+    int rc = carve_scratch(c, [&](Carve &cv) {
+        s.lay(cv, M, nch);
+        d_nr = cv.take<i64>(nch * M); d_np = cv.take<i64>(nch * M); d_tot = cv.take<i64>(2); d_rec = cv.take<i64>(6 * max_records);
+    });
     if (rc) return rc;
-    RupScan s;
-    if ((rc = rup_scan(c, (char *)c->d_scratch, before_in, after_in, &s))) return rc;
-    i64 *d_nr = (i64 *)s.rest, *d_np = d_nr + nch * M, *d_tot = d_np + nch * M, *d_rec = d_tot + 2;
+    if ((rc = rup_scan(c, before_in, after_in, s))) return rc;
     const dim3 cgrid((unsigned)nch, (unsigned)((M + 63) / 64));
     k_rup_runs<false><<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, c->frame0, s.cb, s.ca, s.ce, d_nr, d_np, nullptr);
     k_rup_scan<<<dim3(1), dim3(1024), 0, c->stream>>>(d_nr, d_np, M, nch, d_tot);
@@ -608,30 +583,24 @@ extern "C" int sit_replace_closer(sit_ctx *c, const i64 *records, i64 n, const d
         return SIT_OK;
     }
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, 64 + N * 8 + n * 48 + n_positions * 8 + K * 24 + n_positions * 24);
+    u64 *d_flags;
+    i64 *d_out, *d_rec, *d_owner;
+    double *d_cen, *d_pos;
+    int rc = carve_scratch(c, [&](Carve &cv) {
+        d_flags = cv.take<u64>(2); d_out = cv.take<i64>(N); d_rec = cv.take<i64>(6 * n); d_owner = cv.take<i64>(n_positions);
+        d_cen = cv.take<double>(3 * K); d_pos = cv.take<double>(3 * n_positions);
+    });
     if (rc) return rc;
-    char *p = (char *)c->d_scratch;
-    u64 *d_flags = (u64 *)p; p += 64;
-    i64 *d_out = (i64 *)p; p += N * 8;
-    i64 *d_rec = (i64 *)p; p += n * 48;
-    i64 *d_owner = (i64 *)p; p += n_positions * 8;
-    double *d_cen = (double *)p; p += K * 24;
-    double *d_pos = (double *)p;
     HIP_TRY(c, hipMemcpyAsync(d_out, c->d_labels, (size_t)N * 8, hipMemcpyDeviceToDevice, c->stream));
     if (n > 0) {
-        HIP_TRY(c, hipMemsetAsync(d_flags, 0, 64, c->stream));
+        HIP_TRY(c, hipMemsetAsync(d_flags, 0, 16, c->stream));
         HIP_TRY(c, hipMemcpyAsync(d_rec, records, (size_t)n * 48, hipMemcpyHostToDevice, c->stream));
         k_rc_check<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(d_rec, n, F, M, c->frame0, K, n_positions, d_flags);
         HIP_TRY(c, hipGetLastError());
         u64 *h_flags = (u64 *)c->h_pinned;
         HIP_TRY(c, hipMemcpyAsync(h_flags, d_flags, 16, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (h_flags[1]) {
-            char text[128];
-            snprintf(text, sizeof(text), "index %lld is out of bounds for axis 0 with size %lld", (long long)h_flags[1] - 1, (long long)K);
-            c->msg = text;
-            return SIT_ERR_INVALID;
-        }
+        if (h_flags[1]) return index_out_of_bounds(c, (i64)h_flags[1] - 1, K);
         if (h_flags[0]) {
             char text[160];
             snprintf(text, sizeof(text), "sit_replace_closer: %llu records outside the context (ion, frames, sites or position offset)",
@@ -690,13 +659,14 @@ extern "C" int sit_running_mode(sit_ctx *c, i64 wleft, i64 wright, i64 threshold
     HIP_TRY(c, hipSetDevice(c->device));
     const i64 N = c->N;
     if (N == 0) return SIT_OK;
-    int rc = ensure_scratch(c, N * 8);
+    i64 *d_out;
+    int rc = carve_scratch(c, [&](Carve &cv) { d_out = cv.take<i64>(N); });
     if (rc) return rc;
     k_running_mode<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream>>>(
-        c->d_labels, (i64 *)c->d_scratch, c->F, c->M, wleft, wright, threshold, replace_unknown);
+        c->d_labels, d_out, c->F, c->M, wleft, wright, threshold, replace_unknown);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
-    if (counts && K > 0) return label_counts_of(c, (const i64 *)c->d_scratch, N, K, counts);   // (synchronises)
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)N * 8, hipMemcpyDeviceToHost, c->stream));
+    if (counts && K > 0) return label_counts_of(c, d_out, N, K, counts);   // (synchronises)
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SIT_OK;
 }
@@ -728,21 +698,27 @@ __global__ __launch_bounds__(256) void k_recenter(double *arr, i64 A, const doub
     }
 }
 
+// total_mass_inverse and the per-atom coefficient exactly as :83-92 (left to right)
+static std::vector<double> recenter_coef(i64 A, const double *masses, const double *factors)
+{
+    double tot = 0.0;
+    for (i64 j = 0; j < A; j++) tot += factors[j] * masses[j];
+    const double tmi = 1.0 / tot;
+    std::vector<double> coef((size_t)A);
+    for (i64 j = 0; j < A; j++) coef[(size_t)j] = tmi * factors[j] * masses[j];
+    return coef;
+}
+
 extern "C" int sit_recenter(sit_ctx *c, double *arr, i64 F, i64 A, const double *masses, const double *factors, const double *add3)
 {
     if (!c || !arr || !masses || !factors) return SIT_ERR_INVALID;
     SIT_REQUIRE(c, F >= 0 && A > 0, "sit_recenter: bad shape");
     if (F == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    // total_mass_inverse and the per-atom coefficient exactly as :83-92 (left to right)
-    double tot = 0.0;
-    for (i64 j = 0; j < A; j++) tot += factors[j] * masses[j];
-    const double tmi = 1.0 / tot;
-    std::vector<double> coef((size_t)A);
-    for (i64 j = 0; j < A; j++) coef[(size_t)j] = tmi * factors[j] * masses[j];
-    int rc = ensure_scratch(c, F * A * 24 + A * 8);
+    const std::vector<double> coef = recenter_coef(A, masses, factors);
+    double *d, *dc;
+    int rc = carve_scratch(c, [&](Carve &cv) { d = cv.take<double>(F * A * 3); dc = cv.take<double>(A); });
     if (rc) return rc;
-    double *d = (double *)c->d_scratch, *dc = d + F * A * 3;
     HIP_TRY(c, hipMemcpyAsync(d, arr, (size_t)(F * A) * 24, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dc, coef.data(), (size_t)A * 8, hipMemcpyHostToDevice, c->stream));
     k_recenter<<<dim3((unsigned)F), dim3(256), 0, c->stream>>>(d, A, dc, add3 ? add3[0] : 0.0, add3 ? add3[1] : 0.0, add3 ? add3[2] : 0.0);
@@ -762,14 +738,10 @@ extern "C" int sit_recenter_resident(sit_ctx *c, const double *masses, const dou
     if (c->F == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const i64 A = c->A;
-    double tot = 0.0;                                       // :83-92, left to right
-    for (i64 j = 0; j < A; j++) tot += factors[j] * masses[j];
-    const double tmi = 1.0 / tot;
-    std::vector<double> coef((size_t)A);
-    for (i64 j = 0; j < A; j++) coef[(size_t)j] = tmi * factors[j] * masses[j];
-    int rc = ensure_scratch(c, A * 8);
+    const std::vector<double> coef = recenter_coef(A, masses, factors);
+    double *dc;
+    int rc = carve_scratch(c, [&](Carve &cv) { dc = cv.take<double>(A); });
     if (rc) return rc;
-    double *dc = (double *)c->d_scratch;
     HIP_TRY(c, hipMemcpyAsync(dc, coef.data(), (size_t)A * 8, hipMemcpyHostToDevice, c->stream));
     k_recenter<<<dim3((unsigned)c->F), dim3(256), 0, c->stream>>>(c->d_frames, A, dc, add3 ? add3[0] : 0.0, add3 ? add3[1] : 0.0, add3 ? add3[2] : 0.0);
     HIP_TRY(c, hipGetLastError());

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string>
 #include <vector>
 
@@ -222,6 +223,15 @@ static inline int ensure_scratch(sit_ctx *c, i64 bytes)
     HIP_TRY(c, hipMalloc(&c->d_scratch, (size_t)bytes));
     c->scratch_bytes = bytes;
     return SIT_OK;
+}
+
+// numpy's IndexError text for a site index beyond a table of K sites (_lib.py matches on its first word)
+static inline int index_out_of_bounds(sit_ctx *c, i64 index, i64 K)
+{
+    char text[128];
+    snprintf(text, sizeof(text), "index %lld is out of bounds for axis 0 with size %lld", (long long)index, (long long)K);
+    c->msg = text;
+    return SIT_ERR_INVALID;
 }
 
 // compute units of the context's device, queried once (256 when the query fails)

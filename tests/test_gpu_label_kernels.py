@@ -1,7 +1,8 @@
-"""The label-trajectory kernels (dynamics.hip: JumpAnalysis, assign_to_last_known_site, running windowed mode;
-sites.hip: jump scan, occupancy check, site counts) on adversarial label arrays at edge shapes, against the oracle.
+"""The label-trajectory kernels (dynamics.hip: jump scan, JumpAnalysis, assign_to_last_known_site, running windowed mode;
+sites.hip: occupancy check, site counts) on adversarial label arrays at edge shapes, against the oracle.
 
-The device scans cut the frames into chunks of 256 (DCH / JCH) and carry one state per ion from chunk to chunk and from
+The device scans cut the frames into chunks of 256 (LS_CHUNK of label_scan.h; tests/test_label_scan.py runs the same
+chunk algebra on the CPU at other lengths) and carry one state per ion from chunk to chunk and from
 frame shard to frame shard; the ions sit in groups of 64 lanes, and k_ja_accumulate strides over the ions of a frame
 256 at a time.  The generator below plants, on purpose, what those cuts can get wrong: dwells and unknown streaks that
 span whole chunks, streaks that start or end on a chunk boundary, a first known label after a boundary-crossing streak
@@ -11,7 +12,7 @@ ions making the same jump in one frame, more than 256 columns apart.  `test_gene
 import numpy as np
 import pytest
 
-CH = 256                                             # DCH / JCH of the device scans
+CH = 256                                             # LS_CHUNK of the device scans
 
 # (F, M): every F in {1, 2, 255, 256, 257, 769, 3000} and every M in {1, 63, 64, 65, 300, 448} at least once
 SHAPES = [(1, 65), (2, 1), (255, 64), (256, 63), (257, 300), (769, 448), (3000, 1), (3000, 65), (3000, 448)]
@@ -324,6 +325,28 @@ def test_jumps_and_shard_carry(oracle, F, M, unknown_as_jump):
         s2, _ = c2.jump_sources(unknown_as_jump, l1)
         s1, _ = c1.jump_sources(unknown_as_jump)
         assert np.array_equal(np.concatenate([s1, s2]), src), s
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("with_halo", [False, True])
+def test_forward_scans_of_a_context_without_frames(with_halo):
+    """F = 0: no chunk, so only the carry kernels run; they hand the carried-in state (or the start state) on unchanged."""
+    K, M = 5, 3
+    c = _ctx(np.empty((0, M), dtype=np.int64))
+    last = np.array([2, -1, 4], dtype=np.int64) if with_halo else None
+    other = np.array([7, 1, 300], dtype=np.int64) if with_halo else None
+    for unknown_as_jump in (False, True):
+        rec, lout = c.jump_list(unknown_as_jump, last)
+        src, lout2 = c.jump_sources(unknown_as_jump, last)
+        assert rec.shape == (0, 4) and src.shape == (0, M) and src.dtype == np.int64
+        assert np.array_equal(lout, last if with_halo else [-1] * M) and np.array_equal(lout2, lout)
+    n_ij, tsum, tn, total, nprob, lout, tout = c.jump_analysis(K, last, other)
+    assert not n_ij.any() and not tsum.any() and not tn.any() and not total.any() and nprob == 0
+    assert n_ij.shape == (K, K) and total.shape == (K,)
+    assert np.array_equal(lout, last if with_halo else [-1] * M) and np.array_equal(tout, other if with_halo else [1] * M)
+    labels, fmax, st3, lout, tout = c.assign_last_known(3, last, other)
+    assert labels.shape == (0, M) and fmax.shape == (0,) and not st3.any()
+    assert np.array_equal(lout, last if with_halo else [-1] * M) and np.array_equal(tout, other if with_halo else [0] * M)
 
 
 @pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""GPU: the two-directional label scan of dynamics.hip (``k_rup_*``, ``k_rc_*``) behind ``sit_label_ends``,
+"""GPU: the two-directional label scan of dynamics.hip (``k_label_chunk_summary``, ``k_rup_*``, ``k_rc_*``) behind ``sit_label_ends``,
 ``sit_replace_unassigned``, ``sit_unknown_runs`` and ``sit_replace_closer``, and ``ReplaceUnassignedPositions`` on top of
 them - against the reference's goldens (tests/golden/replace_unassigned_known_answers.npz) and against the numpy brute
 force of tests/replace_ref.py on designed and hand-built label sets.
@@ -14,7 +14,7 @@ from tests import replace_ref as R
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = 256                                          # DCH of dynamics.hip
+CHUNK = 256                                          # LS_CHUNK of label_scan.h
 RG = R.ReplaceGoldens()
 K = R.K_DESIGNED
 
