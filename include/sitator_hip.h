@@ -39,7 +39,8 @@ enum sit_status {
     SIT_ERR_MULTIPLE_OCCUPANCY = 6, /* MultipleOccupancyError, SiteTrajectory.py:219-226    */
     SIT_ERR_NOT_CONVERGED = 7,      /* ValueError, util/DotProdClassifier.pyx:312-313       */
     SIT_ERR_CAPACITY = 8,           /* an internal capacity was exceeded (message says which)*/
-    SIT_RETRY = 9                   /* a deferred sit_fill must be repeated (sit_fill_result)  */
+    SIT_RETRY = 9,                  /* a deferred sit_fill must be repeated (sit_fill_result)  */
+    SIT_ERR_UNASSIGNED = 10         /* RuntimeError, misc/GenerateClampedTrajectory.pyx:73-74 */
 };
 
 /* kind = one of sit_status; frame / index / aux as the matching reference exception:
@@ -342,6 +343,26 @@ int sit_recenter_resident(sit_ctx *ctx, const double *masses, const double *fact
 int sit_speed_spectrum(sit_ctx *ctx, const double *positions, int64_t F, const int64_t *atoms, int64_t n_sel,
                        const double *freqs, const uint8_t *fmask, int64_t workspace_bytes, double *avg,
                        double *band_power, double *spectrum, double *speeds);
+
+/* GenerateClampedTrajectory (misc/GenerateClampedTrajectory.pyx:92-126): out[F, A, 3] (host) holds for every frame and
+ * atom, by role[a]: -1 the atom's real position, -2 fixed_pos[a], m >= 0 the centre of the site that column m of the
+ * resident labels [F, M] names at that frame - as given with wrap != 0, with wrap == 0 the periodic image of the centre
+ * nearest the atom's real position (27-image search between the wrapped position and the wrapped centre, then crystal
+ * centre + floor(crystal position) + image, back to real space, in the reference's operation order: bit-equal).
+ * positions: host [F, A, 3], or NULL for the frames resident after sit_set_frames / sit_upload_fill_fit (F and A must then
+ * be the context's); it is not looked at when no element needs a real position (wrap != 0, no role -1 and
+ * pass_through_unassigned == 0).  fixed_pos [A, 3]; centers [K, 3].  Frames are processed in chunks whose device buffers
+ * (the output, on the host path the staged positions too) fit workspace_bytes (0: SITATOR_CLAMP_WORKSPACE_MB, default
+ * 1024); a frame's result does not depend on the chunking.  A label of -1 on a clamped ion: with pass_through_unassigned
+ * the real position is written; without, the call returns SIT_ERR_UNASSIGNED, *first_unassigned (optional; -1 otherwise)
+ * is the smallest frame * M + column found and nothing is promised about out.  Every label is looked at before anything
+ * is indexed with it: a label >= K fails like sit_jump_analysis (SIT_ERR_INVALID, message starting "index ", IndexError in
+ * Python); a label < -1, a role outside [-2, M), two atoms with the same column, an F or A other than the resident
+ * labels' / frames', a cap below one frame fail with SIT_ERR_INVALID.  Reads only: frames, rows, labels and their
+ * validity stay as they are.                                                                               */
+int sit_clamp_trajectory(sit_ctx *ctx, const double *positions, int64_t F, int64_t A, const int32_t *role,
+                         const double *fixed_pos, const double *centers, int64_t K, int wrap,
+                         int pass_through_unassigned, int64_t workspace_bytes, double *out, int64_t *first_unassigned);
 
 /* ---- frame sharding across GPUs ------------------------------------ */
 

@@ -13,8 +13,8 @@ from .site_trajectory import SiteTrajectory  # noqa: F401
 from .pbc import PBCCalculator  # noqa: F401
 from .dotprod_classifier import DotProdClassifier, LandmarkVectors  # noqa: F401
 from .landmark import LandmarkAnalysis  # noqa: F401
-from .dynamics import (AverageVibrationalFrequency, JumpAnalysis, MergeSitesByDynamics, MergeSitesByThreshold,  # noqa: F401
-                       RemoveUnoccupiedSites, ReplaceUnassignedPositions, SmoothSiteTrajectory)
+from .dynamics import (AverageVibrationalFrequency, GenerateClampedTrajectory, JumpAnalysis, MergeSitesByDynamics,  # noqa: F401
+                       MergeSitesByThreshold, RemoveUnoccupiedSites, ReplaceUnassignedPositions, SmoothSiteTrajectory)
 from .merging import MergeSites, MergeSitesError, MergedSitesTooDistantError  # noqa: F401
 from .recenter import RecenterTrajectory  # noqa: F401
 

@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SITATOR_LIB") or os.path.join(_HERE, "lib", "libsitator_hip.so")     # SITATOR_LIB: another build (A/B runs)
 
 OK, E_INVALID, E_HIP, E_STATIC_THRESHOLD, E_STATIC_UNASSIGNED, E_ZERO_LANDMARK, \
-    E_MULTIPLE_OCCUPANCY, E_NOT_CONVERGED, E_CAPACITY, RETRY = range(10)
+    E_MULTIPLE_OCCUPANCY, E_NOT_CONVERGED, E_CAPACITY, RETRY, E_UNASSIGNED = range(11)
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
@@ -101,6 +101,7 @@ SIGNATURES = {
     "sit_recenter_resident": (C.c_int, [_vp, _dp, _dp, _dp]),
     "sit_recenter": (C.c_int, [_vp, _dp, i64, i64, _dp, _dp, _dp]),
     "sit_speed_spectrum": (C.c_int, [_vp, _dp, i64, _ip, i64, _dp, _u8p, i64, _dp, _dp, _dp, _dp]),
+    "sit_clamp_trajectory": (C.c_int, [_vp, _dp, i64, i64, _i32p, _dp, _dp, i64, C.c_int, C.c_int, i64, _dp, _ip]),
     "sit_comm_unique_id": (C.c_int, [_u8p]),
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
     "sit_comm_destroy": (C.c_int, [_vp]),
@@ -728,6 +729,40 @@ class HipContext(object):
             None if spec is None else spec.ctypes.data_as(_dp), None if spd is None else _d(spd)))
         return avg, power, spec, spd
 
+    # -- GenerateClampedTrajectory: reads labels and frames only (labels_version, rows and labels stay)
+    def clamp_trajectory(self, role, fixed_pos, centers, wrap, pass_through_unassigned, positions=None, workspace_bytes=0):
+        """``float64[F, A, 3]`` (``sit_clamp_trajectory``): per atom, by ``role[a]``, its real position (-1),
+        ``fixed_pos[a]`` (-2) or the centre of the site that column ``role[a]`` of the resident labels names - as given
+        with ``wrap``, else its periodic image nearest the atom's real position.  ``positions``: a host ``[F, A, 3]``
+        float64 array; without it the frames resident after ``set_frames`` are read (none are needed with ``wrap``, no
+        role -1 and no pass-through).  ``workspace_bytes``: cap on the device buffers of a chunk of frames (0: the default
+        of 1 GiB).  An unassigned label without ``pass_through_unassigned`` raises ``errors.UnassignedClampError`` (a
+        ``RuntimeError``; ``.first_unassigned`` = the smallest frame * M + column), a label ``>= len(centers)``
+        ``IndexError``, any other argument that does not fit the context ``ValueError``."""
+        role = np.ascontiguousarray(role, dtype=np.int32).reshape(-1)
+        A = len(role)
+        fixed_pos = _f64(fixed_pos).reshape(A, 3)
+        centers = _f64(centers).reshape(-1, 3)
+        if positions is not None:
+            positions = _f64(positions)
+            assert positions.ndim == 3 and positions.shape[1:] == (A, 3)
+            F = positions.shape[0]
+        else:
+            F = self.F
+        out = np.empty((F, A, 3))
+        first = i64(-1)
+        rc = self.lib.sit_clamp_trajectory(
+            self._h, None if positions is None else _d(positions), int(F), int(A), role.ctypes.data_as(_i32p), _d(fixed_pos),
+            _d(centers), len(centers), int(bool(wrap)), int(bool(pass_through_unassigned)), int(workspace_bytes), _d(out),
+            C.byref(first))
+        if rc == E_UNASSIGNED:
+            raise errors.UnassignedClampError(first.value)
+        if rc == E_INVALID and self.message().startswith("index "):
+            # a label beyond the sites: the reference's centers_c[at_site] reads past the table (GenerateClampedTrajectory.pyx:99)
+            raise IndexError(self.message())
+        self._check(rc)
+        return out
+
     # ---- RCCL exchange of the frame-sharded path (csrc/comm.hip) ----
     def comm_create(self, unique_id, rank, world):
         uid = np.frombuffer(bytes(unique_id), dtype=np.uint8).copy()
@@ -784,6 +819,13 @@ class HipContext(object):
         names = ["fill", "fit", "predict", "gram", "site_centers", "occupancy", "h2d"]
         return {k: (float(t[8 + i]), int(t[16 + i])) for i, k in enumerate(names)}
 
+    def clamp_kernel_time(self):
+        """(sum in ms, number) of the ``k_clamp`` launches of ``clamp_trajectory`` since the context was made: the
+        kernel alone, without the copies of a call (slot 7 of ``sit_timers``)."""
+        t = np.zeros(24)
+        self.lib.sit_timers(self._h, _d(t), 24)
+        return float(t[15]), int(t[23])
+
     def info(self):
         v = np.zeros(29)
         self.lib.sit_info(self._h, _d(v), 29)
@@ -826,6 +868,6 @@ for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "a
               "gram_limbs", "weighted_row_sums", "weighted_row_sums_limbs", "best_match", "best_match_groups",
               "site_anchors", "site_sums", "check_occupancy", "site_counts", "cooccupancy", "jump_sources", "jump_list",
               "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
-              "unknown_runs", "replace_closer"):
+              "unknown_runs", "replace_closer", "clamp_trajectory"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

@@ -790,6 +790,28 @@ static int upload_staged(sit_ctx *c, hipStream_t stream, hipEvent_t *slot_ev, vo
     return rc;
 }
 
+// upload_staged for callers without slot events of their own (clamp.hip): small copies go straight to the runtime
+int upload_staged_sync(sit_ctx *c, void *dst, const void *src, size_t bytes)
+{
+    if (bytes == 0) return SIT_OK;
+    if (bytes < RING_CHUNK || !c->copy_stream) {
+        HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return SIT_OK;
+    }
+    hipEvent_t ev[RING_SLOTS] = {};
+    for (int i = 0; i < RING_SLOTS; i++)
+        if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
+            for (int q = 0; q < i; q++) (void)hipEventDestroy(ev[q]);
+            c->msg = "hipEventCreate failed"; return SIT_ERR_HIP;
+        }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));                 // whatever read dst before is done
+    const int rc = upload_staged(c, c->copy_stream, ev, dst, src, bytes);
+    for (int i = 0; i < RING_SLOTS; i++) (void)hipEventDestroy(ev[i]);
+    if (rc) c->msg = "staged host-to-device copy failed";
+    return rc;
+}
+
 // Device -> host copy into a pageable buffer through the same ring: the DMA of a slot is enqueued on `stream`, copy
 // threads move finished slots to their place.  A plain hipMemcpy of 0.9 GB into a fresh numpy array runs at 18 GB/s
 // (one thread copies out of the runtime's staging buffer and takes the page faults of the new array); eight threads

@@ -23,7 +23,7 @@ struct Pbc {
     double cen[3];
 };
 
-enum { T_FILL = 0, T_FIT = 1, T_PREDICT = 2, T_GRAM = 3, T_CENTERS = 4, T_OCC = 5, T_H2D = 6, T_N = 8 };
+enum { T_FILL = 0, T_FIT = 1, T_PREDICT = 2, T_GRAM = 3, T_CENTERS = 4, T_OCC = 5, T_H2D = 6, T_CLAMP = 7, T_N = 8 };
 
 #define SIT_NO_ERROR_KEY 0xFFFFFFFFFFFFFFFFull
 
@@ -506,6 +506,7 @@ int wide_list_carve(sit_ctx *c, int nseg, i64 seg_cap, unsigned **wcount, i32 **
 // cluster.hip: the rows k_fill3 listed (segments of the scratch buffer), then the label counts
 int predict_listed_rows(sit_ctx *c, double threshold, i32 *wlist, unsigned *wcount, i64 seg_cap, int nseg);
 int download_staged(sit_ctx *c, hipStream_t stream, void *dst, const void *src, size_t bytes);   // fill.hip: large read-backs
+int upload_staged_sync(sit_ctx *c, void *dst, const void *src, size_t bytes);   // fill.hip: a pageable host buffer through the pinned ring, done on return
 int reset_fill_words(sit_ctx *c);                                  // ctx.hip: error key and counters in one launch
 void fill_ring_free(sit_ctx *c);                                   // fill.hip
 int fill_results_landed(sit_ctx *c);                               // fill.hip: decode the deferred results that have landed

@@ -14,6 +14,8 @@ device-resident site assignments:
 * ``AverageVibrationalFrequency``  (reference ``sitator/dynamics/AverageVibrationalFrequency.py:30-61``; speeds, their
   exact-length Fourier transform and the band average per atom on the device, also straight from the trajectory a
   ``LandmarkAnalysis`` left resident)
+* ``GenerateClampedTrajectory``  (reference ``sitator/misc/GenerateClampedTrajectory.pyx:13-128``; one pass of the device
+  over the resident labels and the frames, also straight from the trajectory a ``LandmarkAnalysis`` left resident)
 """
 import logging
 import operator
@@ -557,3 +559,137 @@ class AverageVibrationalFrequency(object):
             return self._over_atoms(np.empty(0), np.empty(0), return_stdev)
         avg_freqs, band_power, _, _ = ctx.speed_spectrum(freqs, fmask, atoms=atoms)
         return self._over_atoms(avg_freqs, band_power, return_stdev)
+
+
+class GenerateClampedTrajectory(object):
+    """A real-space trajectory in which the atoms of ``clamp_mask`` stand on fixed positions: a static atom on its
+    position in the network's structure, a mobile atom on the centre of the site it is assigned to at that frame; every
+    other atom keeps its real position (reference ``misc/GenerateClampedTrajectory.pyx``).
+
+    ``wrap``: ``True`` writes the centres as they are; ``False`` (the default) the periodic image of the centre nearest
+    the atom's real position, which turns an unwrapped real trajectory into an unwrapped clamped one.
+    ``pass_through_unassigned``: ``True`` writes the real position of a mobile atom to clamp at the frames where it is
+    unassigned; ``False`` raises the reference's ``RuntimeError`` when there is such a frame.
+
+    One HIP kernel (``sit_clamp_trajectory``) makes every frame from the device-resident labels, in chunks of frames that
+    are copied back as they are finished; the arithmetic of a clamped point follows the reference operation by operation
+    and the result is bit-equal to it wherever the reference runs.
+
+    Deviations from the reference, whose own copy does not get far:
+
+    * The stock module is rejected by Cython 3 (``:117``), and once compiled ``run()`` raises ``IndexError`` at ``:71``
+      for every structure with a static atom: it indexes the ``n_mobile`` label columns with a mask over all atoms, and
+      its loop (``:94-99``) reads the label column with the atom's index.  Here the label column of a mobile atom is its
+      rank among the mobile atoms, which is what the docstring describes and what the reference does where it runs
+      (every atom mobile).
+    * A mask that selects no mobile atom is valid.  The reference raises numpy's ``ValueError`` for the minimum of an
+      empty array (``:73``).
+    * A clamped atom that is neither static nor mobile gets its position in the structure; the reference leaves its
+      entries of ``np.empty`` as they are.
+    * Without a real trajectory, a mobile atom to clamp that needs its real position (``wrap=False``, or an unassigned
+      frame to pass through) raises ``RuntimeError``; the reference dereferences ``None``.
+    * Trajectories are float64 only: another dtype raises the ``ValueError`` ``AverageVibrationalFrequency`` raises.
+    * A label ``>= n_sites`` raises ``IndexError`` (the reference reads past the centre table), a label below -1
+      ``ValueError``.
+    * On frame shards ``run(st)`` clamps the frames of its shard; nothing is exchanged and nothing gathered."""
+
+    NO_REAL_TRAJ_MSG = ("This `SiteTrajectory` has no real-space trajectory, but the given clamp mask leaves some atoms "
+                        "unclamped.")
+
+    def __init__(self, wrap=False, pass_through_unassigned=False):
+        self.wrap = wrap
+        self.pass_through_unassigned = pass_through_unassigned
+
+    @staticmethod
+    def _roles(sn, clamp_mask):
+        """``(role[n_atoms] int32, clamp_mask)``: -1 pass through, -2 the structure's position, ``m >= 0`` label column
+        ``m`` - the rank of the atom among the mobile ones."""
+        n_atoms = len(sn.structure)
+        if clamp_mask is None:
+            clamp_mask = np.ones(n_atoms, dtype=bool)
+        clamp_mask = np.asarray(clamp_mask)
+        if clamp_mask.dtype != np.bool_ or clamp_mask.shape != (n_atoms,):
+            raise ValueError("clamp_mask must be a boolean mask over the %d atoms of the structure" % n_atoms)
+        mobile = np.asarray(sn.mobile_mask, dtype=bool)
+        role = np.full(n_atoms, -1, dtype=np.int32)
+        role[clamp_mask] = -2
+        rank = np.cumsum(mobile) - 1
+        sel = clamp_mask & mobile
+        role[sel] = rank[sel]
+        return role, clamp_mask
+
+    def _call(self, ctx, sn, role, positions, have_positions):
+        centers = np.asarray(sn.centers, dtype=np.float64).reshape(-1, 3) if sn.n_sites > 0 else np.zeros((0, 3))
+        fixed = np.asarray(sn.structure.get_positions(), dtype=np.float64)
+        clamps_mobile = bool(np.any(role >= 0))
+        if not have_positions:
+            if np.any(role == -1):
+                raise RuntimeError(self.NO_REAL_TRAJ_MSG)                                # :59-60
+            if clamps_mobile and not self.wrap:
+                raise RuntimeError("This `SiteTrajectory` has no real-space trajectory, which clamping with wrap=False "
+                                   "needs for every mobile atom to clamp.")
+            try:
+                # nothing to read but labels and centres; an unassigned label shows in the same pass
+                return ctx.clamp_trajectory(role, fixed, centers, True, False)
+            except errors.UnassignedClampError:
+                if not self.pass_through_unassigned:
+                    raise
+                raise RuntimeError("This `SiteTrajectory` has no real-space trajectory, but a mobile atom to clamp is "
+                                   "unassigned at some frame and `pass_through_unassigned` would pass its position through.")
+        return ctx.clamp_trajectory(role, fixed, centers, self.wrap, self.pass_through_unassigned, positions=positions)
+
+    def run(self, st, clamp_mask=None):
+        """``float64[n_frames, n_atoms, 3]``.  ``clamp_mask``: boolean over the atoms of the structure, any mixture of
+        static and mobile ones; ``None``: all.  The labels are the trajectory's (``st._device()``), the positions
+        ``st.real_trajectory``; nothing of it is sent to the GPU when no element needs a real position (``wrap=True``,
+        every atom clamped, no pass-through)."""
+        assert isinstance(st, SiteTrajectory)
+        sn = st.site_network
+        role, clamp_mask = self._roles(sn, clamp_mask)
+        real = st.real_trajectory
+        if real is None and not np.all(clamp_mask):
+            raise RuntimeError(self.NO_REAL_TRAJ_MSG)
+        if real is not None:
+            real = np.asarray(real)
+            if real.dtype != np.float64:
+                raise ValueError("Buffer dtype mismatch, expected 'double' but got '%s'" % real.dtype)
+        ctx = st._device()
+        needs = bool(np.any(role == -1)) or (bool(np.any(role >= 0)) and (not self.wrap or self.pass_through_unassigned))
+        if real is not None and not needs:
+            return ctx.clamp_trajectory(role, np.asarray(sn.structure.get_positions(), dtype=np.float64),
+                                        np.asarray(sn.centers, dtype=np.float64).reshape(-1, 3) if sn.n_sites > 0
+                                        else np.zeros((0, 3)), True, False)
+        return self._call(ctx, sn, role, real, real is not None)
+
+    def run_for_analysis(self, la, st=None, clamp_mask=None):
+        """The same from the frames a ``LandmarkAnalysis`` that has run left on its GPU: no upload.  ``st``: the
+        trajectory to take the labels from - ``None``: the one ``la.run()`` returned; otherwise one that shares the
+        analysis' device context (that trajectory after ``assign_to_last_known_site`` or an edit of ``st.traj``, a copy
+        ``st[:]``), whose labels are brought up to date on the device first.  A trajectory with a context of its own (the
+        result of ``SmoothSiteTrajectory`` or ``ReplaceUnassignedPositions``, one made by the caller) raises
+        ``ValueError``: use ``run(st)`` with its real trajectory.
+
+        The frames are those ``run()`` received, as they were at that time.  Raises ``ValueError`` if the analysis
+        recentred the frames on the device (``recenter_masses``) and ``NotImplementedError`` after a run over frame shards
+        (``comm`` of more than one rank, ``devices=[...]``), as ``AverageVibrationalFrequency.compute_for_analysis``."""
+        la._need_run()
+        if getattr(la, "_children", None) is not None or la._comm.size > 1 or la._ctx is None:
+            raise NotImplementedError("GenerateClampedTrajectory.run_for_analysis needs all frames of the trajectory on "
+                                      "one GPU; this analysis ran over frame shards (use run(st) on every shard)")
+        if la._recenter_masses is not None:
+            raise ValueError("The analysis recentred its frames on the device (recenter_masses): they are not the "
+                             "trajectory run() was given; use run(st) on that")
+        if st is None:
+            ref = getattr(la, "_result", None)
+            st = ref() if ref is not None else None
+            if st is None:
+                raise ValueError("The trajectory this analysis returned does not exist any more; pass `st`")
+        assert isinstance(st, SiteTrajectory)
+        if st._ctx is not la._ctx:
+            raise ValueError("`st` does not share the device context of this analysis; use run(st)")
+        sn = st.site_network
+        role, _ = self._roles(sn, clamp_mask)
+        ctx = st._device()
+        if len(role) != ctx.A:
+            raise ValueError("The structure has %d atoms, the resident frames %d" % (len(role), ctx.A))
+        return self._call(ctx, sn, role, None, True)

@@ -65,6 +65,18 @@ class InsufficientSitesError(SiteAnaysisError):
         self.n_mobile = n_mobile
 
 
+class UnassignedClampError(RuntimeError):
+    """``GenerateClampedTrajectory``: a mobile atom to clamp is unassigned and ``pass_through_unassigned`` is off (the
+    reference's ``RuntimeError``, ``misc/GenerateClampedTrajectory.pyx:73-74``, with its text).  Attribute:
+    ``first_unassigned``, the smallest ``frame * n_mobile + mobile_atom`` of the trajectory's frames that is."""
+
+    def __init__(self, first_unassigned):
+        super(UnassignedClampError, self).__init__(
+            "The mobile atoms indicated for clamping are unassigned at some point during the trajectory and "
+            "`pass_through_unassigned` is set to False. Try `assign_to_last_known_site()`?")
+        self.first_unassigned = first_unassigned
+
+
 class DeviceDomainError(Exception):
     """Internal: a domain error reported by the C-ABI before it is mapped to the classes above."""
 

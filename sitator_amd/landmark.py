@@ -14,6 +14,7 @@ Extra, reference-preserving keywords: ``comm`` (frame sharding across GPUs, see 
 """
 import importlib
 import os
+import weakref
 import logging
 import time
 
@@ -269,6 +270,7 @@ class LandmarkAnalysis(object):
         self.wall_timings = wall
         self.fit_timings = getattr(self._landmark_vectors, "fit_timings", None)     # dotprod: fit / exchange / merge seconds
         self._has_run = True
+        self._result = weakref.ref(out_st)     # GenerateClampedTrajectory.run_for_analysis: the default trajectory
         return out_st
 
     def _run_on_devices(self, sn, frames):
