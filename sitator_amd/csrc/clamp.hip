@@ -205,7 +205,7 @@ extern "C" int sit_clamp_trajectory(sit_ctx *c, const double *positions, i64 F, 
         const i64 nf = f0 + Fc < F ? Fc : F - f0;
         const size_t bytes = (size_t)(nf * frame_bytes);
         if (host_pos) {
-            if ((rc = upload_staged_sync(c, buf.pos, (const char *)positions + f0 * frame_bytes, bytes))) return rc;
+            if ((rc = copy_to_device(c, buf.pos, (const char *)positions + f0 * frame_bytes, bytes))) return rc;
             a.pos = buf.pos;
         } else {
             a.pos = any_need ? c->d_frames + f0 * A * 3 : nullptr;
@@ -218,8 +218,7 @@ extern "C" int sit_clamp_trajectory(sit_ctx *c, const double *positions, i64 F, 
         t.stop();
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(h_status, d_status, 24, hipMemcpyDeviceToHost, c->stream));
-        if (bytes >= ((size_t)64 << 20)) { if ((rc = download_staged(c, c->stream, (char *)out + f0 * frame_bytes, buf.out, bytes))) return rc; }
-        else HIP_TRY(c, hipMemcpyAsync((char *)out + f0 * frame_bytes, buf.out, bytes, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = copy_to_host(c, (char *)out + f0 * frame_bytes, buf.out, bytes))) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (h_status[1]) return index_out_of_bounds(c, (i64)h_status[1] - 1, K);
         if (h_status[2]) {

@@ -15,7 +15,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <thread>
 #include <vector>
 
@@ -735,137 +734,6 @@ extern "C" int sit_fill(sit_ctx *c, const sit_fill_params *p, i64 *n_all_zero, s
     return SIT_ERR_CAPACITY;
 }
 
-// Host -> device copy of part of a pageable buffer through a ring of pinned staging buffers: copy threads (8;
-// SITATOR_COPY_THREADS) fill 4 MB slots, each slot leaves by DMA as soon as it is staged - the pieces alternating between
-// TWO streams - and is reused once its DMA has finished.  Measured on the MI355X box (scratch/ring_probe.hip, 1.38 GB):
-// a plain hipMemcpy of pageable memory 56 GB/s (but it holds the runtime's lock against other threads' launches while
-// it runs); this ring with ONE stream 46 GB/s whatever the slots, piece size, threads, pinned-memory flags or way of
-// waiting (36-40 GB/s beside the fit's kernels: until round 4 the fit was the longer leg and nobody noticed); with two
-// streams 55 GB/s.  Returns when the whole range has arrived.
-#define RING_SLOTS 16
-#define RING_CHUNK ((size_t)4 << 20)
-static std::mutex g_ring_mutex;
-static char *g_ring = nullptr;
-
-static int upload_staged(sit_ctx *c, hipStream_t stream, hipEvent_t *slot_ev, void *dst, const void *src, size_t bytes)
-{
-    hipStream_t two[2] = {stream, c->copy_stream2 ? c->copy_stream2 : stream};
-    std::lock_guard<std::mutex> lock(g_ring_mutex);
-    if (!g_ring && hipHostMalloc((void **)&g_ring, RING_SLOTS * RING_CHUNK) != hipSuccess) { g_ring = nullptr; return SIT_ERR_HIP; }
-    const size_t nchunks = (bytes + RING_CHUNK - 1) / RING_CHUNK;
-    static const int want_threads = [] { const char *v = getenv("SITATOR_COPY_THREADS"); const int n = v ? atoi(v) : 0; return n >= 1 && n <= 32 ? n : 8; }();
-    const int nthreads = (int)std::min<size_t>((size_t)want_threads, nchunks);
-    std::vector<std::atomic<int>> staged(nchunks);
-    std::atomic<long long> released(RING_SLOTS), next(0);
-    for (auto &f : staged) f.store(0);
-    char *ring = g_ring;
-    auto worker = [&]() {
-        for (;;) {
-            const long long i = next.fetch_add(1);
-            if (i >= (long long)nchunks) return;
-            while (released.load(std::memory_order_acquire) <= i) std::this_thread::sleep_for(std::chrono::microseconds(10));
-            const size_t off = (size_t)i * RING_CHUNK, n = std::min(RING_CHUNK, bytes - off);
-            memcpy(ring + (size_t)(i % RING_SLOTS) * RING_CHUNK, (const char *)src + off, n);
-            staged[(size_t)i].store(1, std::memory_order_release);
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nthreads; t++) pool.emplace_back(worker);
-    int rc = SIT_OK;
-    for (size_t i = 0; i < nchunks; i++) {
-        while (!staged[i].load(std::memory_order_acquire)) std::this_thread::sleep_for(std::chrono::microseconds(10));
-        const size_t off = i * RING_CHUNK, n = std::min(RING_CHUNK, bytes - off);
-        const int slot = (int)(i % RING_SLOTS);
-        if (rc == SIT_OK && (hipMemcpyAsync((char *)dst + off, ring + (size_t)slot * RING_CHUNK, n, hipMemcpyHostToDevice, two[i & 1]) != hipSuccess ||
-                             hipEventRecord(slot_ev[slot], two[i & 1]) != hipSuccess)) rc = SIT_ERR_HIP;
-        if (i + 1 >= RING_SLOTS / 2) {          // the slot of the oldest chunk in flight is handed back once its DMA is done
-            const size_t done = i + 1 - RING_SLOTS / 2;
-            if (rc == SIT_OK && hipEventSynchronize(slot_ev[done % RING_SLOTS]) != hipSuccess) rc = SIT_ERR_HIP;
-            released.store((long long)(done + 1 + RING_SLOTS), std::memory_order_release);
-        }
-    }
-    released.store((long long)nchunks + RING_SLOTS, std::memory_order_release);
-    for (auto &t : pool) t.join();
-    if (rc == SIT_OK && (hipStreamSynchronize(two[0]) != hipSuccess || hipStreamSynchronize(two[1]) != hipSuccess)) rc = SIT_ERR_HIP;
-    return rc;
-}
-
-// upload_staged for callers without slot events of their own (clamp.hip): small copies go straight to the runtime
-int upload_staged_sync(sit_ctx *c, void *dst, const void *src, size_t bytes)
-{
-    if (bytes == 0) return SIT_OK;
-    if (bytes < RING_CHUNK || !c->copy_stream) {
-        HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return SIT_OK;
-    }
-    hipEvent_t ev[RING_SLOTS] = {};
-    for (int i = 0; i < RING_SLOTS; i++)
-        if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
-            for (int q = 0; q < i; q++) (void)hipEventDestroy(ev[q]);
-            c->msg = "hipEventCreate failed"; return SIT_ERR_HIP;
-        }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));                 // whatever read dst before is done
-    const int rc = upload_staged(c, c->copy_stream, ev, dst, src, bytes);
-    for (int i = 0; i < RING_SLOTS; i++) (void)hipEventDestroy(ev[i]);
-    if (rc) c->msg = "staged host-to-device copy failed";
-    return rc;
-}
-
-// Device -> host copy into a pageable buffer through the same ring: the DMA of a slot is enqueued on `stream`, copy
-// threads move finished slots to their place.  A plain hipMemcpy of 0.9 GB into a fresh numpy array runs at 18 GB/s
-// (one thread copies out of the runtime's staging buffer and takes the page faults of the new array); eight threads
-// (SITATOR_D2H_THREADS) share both.  Returns when everything has arrived.
-int download_staged(sit_ctx *c, hipStream_t stream, void *dst, const void *src, size_t bytes)
-{
-    if (bytes == 0) return SIT_OK;
-    std::lock_guard<std::mutex> lock(g_ring_mutex);
-    if (!g_ring && hipHostMalloc((void **)&g_ring, RING_SLOTS * RING_CHUNK) != hipSuccess) { g_ring = nullptr; c->msg = "pinned staging ring"; return SIT_ERR_HIP; }
-    hipEvent_t ev[RING_SLOTS] = {};
-    for (int i = 0; i < RING_SLOTS; i++)
-        if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming) != hipSuccess) {
-            for (int q = 0; q < i; q++) (void)hipEventDestroy(ev[q]);
-            c->msg = "hipEventCreate failed"; return SIT_ERR_HIP;
-        }
-    const size_t nchunks = (bytes + RING_CHUNK - 1) / RING_CHUNK;
-    static const int want_threads = [] { const char *v = getenv("SITATOR_D2H_THREADS"); const int n = v ? atoi(v) : 0; return n >= 1 && n <= 32 ? n : 8; }();   // eight: the page faults of the fresh destination are the cost (C3: 0.092 -> 0.070 s from four)
-    const int nthreads = (int)std::min<size_t>((size_t)want_threads, nchunks);
-    std::vector<std::atomic<int>> freed(nchunks);
-    for (auto &f : freed) f.store(0);
-    std::atomic<long long> issued(0), next(0);
-    std::atomic<int> failed(0);
-    char *ring = g_ring;
-    auto worker = [&]() {
-        if (hipSetDevice(c->device) != hipSuccess) failed.store(1);
-        for (;;) {
-            const long long i = next.fetch_add(1);
-            if (i >= (long long)nchunks) return;
-            while (issued.load(std::memory_order_acquire) <= i && !failed.load()) std::this_thread::sleep_for(std::chrono::microseconds(10));
-            const int slot = (int)(i % RING_SLOTS);
-            if (!failed.load() && hipEventSynchronize(ev[slot]) != hipSuccess) failed.store(1);
-            const size_t off = (size_t)i * RING_CHUNK, n = std::min(RING_CHUNK, bytes - off);
-            if (!failed.load()) memcpy((char *)dst + off, ring + (size_t)slot * RING_CHUNK, n);
-            freed[(size_t)i].store(1, std::memory_order_release);
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 0; t < nthreads; t++) pool.emplace_back(worker);
-    for (size_t i = 0; i < nchunks && !failed.load(); i++) {
-        if (i >= RING_SLOTS)
-            while (!freed[i - RING_SLOTS].load(std::memory_order_acquire)) std::this_thread::sleep_for(std::chrono::microseconds(10));
-        const size_t off = i * RING_CHUNK, n = std::min(RING_CHUNK, bytes - off);
-        const int slot = (int)(i % RING_SLOTS);
-        if (hipMemcpyAsync(ring + (size_t)slot * RING_CHUNK, (const char *)src + off, n, hipMemcpyDeviceToHost, stream) != hipSuccess ||
-            hipEventRecord(ev[slot], stream) != hipSuccess) failed.store(1);
-        issued.store((long long)i + 1, std::memory_order_release);
-    }
-    if (failed.load()) issued.store((long long)nchunks, std::memory_order_release);
-    for (auto &t : pool) t.join();
-    for (int i = 0; i < RING_SLOTS; i++) (void)hipEventDestroy(ev[i]);
-    if (failed.load()) { (void)hipStreamSynchronize(stream); c->msg = "staged device-to-host copy failed"; return SIT_ERR_HIP; }
-    return SIT_OK;
-}
-
 // sit_set_frames + sit_fill (rows stored) + sit_fit_reset + sit_fit_push_stored_rows in one call, with the upload
 // overlapped: a helper thread sends the trajectory to the GPU in chunks on a copy stream while this thread fills the
 // chunks that have arrived and streams their rows through the fit (fit_centers is an ordered stream over the rows, so
@@ -931,7 +799,7 @@ extern "C" int sit_upload_fill_fit(sit_ctx *c, const double *frames, i64 F, i64 
     int nch = (int)(F / chunk_frames_min);
     nch = nch > 16 ? 16 : (nch < 2 ? 2 : nch);
     const i64 cf = (F + nch - 1) / nch;
-    // events of the chunks and of the ring slots: destroyed on every way out of this function
+    // events of the chunks: destroyed on every way out of this function
     struct Events {
         std::vector<hipEvent_t> ev;
         ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
@@ -940,11 +808,9 @@ extern "C" int sit_upload_fill_fit(sit_ctx *c, const double *frames, i64 F, i64 
             for (size_t i = 0; i < n; i++) HIP_TRY(c, hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
             return SIT_OK;
         }
-    } chunk_events, slot_events;
+    } chunk_events;
     if ((rc = chunk_events.make(c, (size_t)nch))) return rc;
-    if ((rc = slot_events.make(c, RING_SLOTS))) return rc;
     std::vector<hipEvent_t> &ev = chunk_events.ev;
-    hipEvent_t *slot_ev = slot_events.ev.data();
     std::atomic<int> issued(0), failed(0);
     const bool merge = !(getenv("SITATOR_PIPE_MERGE") && getenv("SITATOR_PIPE_MERGE")[0] == '0');
     if (dbgpipe) { (void)hipStreamSynchronize(c->stream); fprintf(stderr, "  buffers and tables ready at %.1f ms\n", since()); }
@@ -954,8 +820,7 @@ extern "C" int sit_upload_fill_fit(sit_ctx *c, const double *frames, i64 F, i64 
             if (dbgpipe) fprintf(stderr, "  upload of chunk %d starts at %.1f ms\n", i, since());
             const i64 lo = i * cf, hi = std::min<i64>(F, lo + cf);
             if (!failed.load() && hi > lo &&
-                (upload_staged(c, c->copy_stream, slot_ev, (char *)c->d_frames + lo * A * 24, (const char *)frames + lo * A * 24,
-                               (size_t)((hi - lo) * A * 24)) != SIT_OK ||
+                (upload_range(c, (char *)c->d_frames + lo * A * 24, (const char *)frames + lo * A * 24, (size_t)((hi - lo) * A * 24)) != SIT_OK ||
                  hipEventRecord(ev[(size_t)i], c->copy_stream) != hipSuccess)) failed.store(1);
             issued.store(i + 1, std::memory_order_release);
         }

@@ -31,7 +31,7 @@ struct sit_ctx {
     int device = 0;
     int num_cu = 0;                                            // compute units of the device (queried once)
     hipStream_t stream = nullptr;
-    hipStream_t copy_stream = nullptr, copy_stream2 = nullptr; // uploads of sit_upload_fill_fit (fill.hip): the pieces alternate between them
+    hipStream_t copy_stream = nullptr, copy_stream2 = nullptr; // staged uploads (transfer.hip): the pieces alternate between them
     hipEvent_t tev0[T_N] = {nullptr}, tev1[T_N] = {nullptr};   // per-stage event pairs
     bool tpending[T_N] = {false};                              // recorded, not yet read
     void *h_pinned = nullptr;                                  // small pinned read-back buffer (256 bytes)
@@ -505,8 +505,10 @@ int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo = 0,
 int wide_list_carve(sit_ctx *c, int nseg, i64 seg_cap, unsigned **wcount, i32 **wlist);
 // cluster.hip: the rows k_fill3 listed (segments of the scratch buffer), then the label counts
 int predict_listed_rows(sit_ctx *c, double threshold, i32 *wlist, unsigned *wcount, i64 seg_cap, int nseg);
-int download_staged(sit_ctx *c, hipStream_t stream, void *dst, const void *src, size_t bytes);   // fill.hip: large read-backs
-int upload_staged_sync(sit_ctx *c, void *dst, const void *src, size_t bytes);   // fill.hip: a pageable host buffer through the pinned ring, done on return
+// transfer.hip: copies between pageable host memory and the device, the large ones through the pinned staging ring
+int upload_range(sit_ctx *c, void *dst, const void *src, size_t bytes);     // on the copy streams, from sit_upload_fill_fit's helper thread; done on return
+int copy_to_device(sit_ctx *c, void *dst, const void *src, size_t bytes);   // done on return
+int copy_to_host(sit_ctx *c, void *dst, const void *src, size_t bytes);     // behind c->stream; done on return or enqueued on c->stream
 int reset_fill_words(sit_ctx *c);                                  // ctx.hip: error key and counters in one launch
 void fill_ring_free(sit_ctx *c);                                   // fill.hip
 int fill_results_landed(sit_ctx *c);                               // fill.hip: decode the deferred results that have landed

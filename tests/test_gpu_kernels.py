@@ -170,18 +170,25 @@ def test_frames_too_large_for_lds_take_the_general_kernel(oracle):
     assert rc == _lib.E_STATIC_THRESHOLD and (err.frame, err.index) == (1, 4321)
 
 
-@pytest.mark.parametrize("pipeline", [False, True])
+@pytest.mark.parametrize("pipeline", [False, True, "small_ring"])
 def test_rows_wider_than_the_measured_width_are_filled_again_at_the_rigorous_width(pipeline, monkeypatch):
     """The rows get as many slots as the leading frames need (+2), not the loose table's longest list; a later row that
     needs more raises the kernel's capacity flag and the fill is repeated at the rigorous width.  Forced here with a
     width of 3 on the ragged C5 host (rows hold up to 13 entries): same labels and vectors as with the rigorous width,
-    through the separate calls and through the pipelined call."""
+    through the separate calls, through the pipelined call, and through the pipelined call with ring chunks so small
+    that every pipeline chunk laps the staging ring."""
     from sitator_amd import LandmarkAnalysis, SiteNetwork, Structure, synth
     host = synth.config_host("C5")
     gen = synth.TrajectoryGenerator(host, 160, seed=12)
     frames = gen.generate(96)
     monkeypatch.setenv("SITATOR_PIPELINE", "1" if pipeline else "0")
     monkeypatch.setenv("SITATOR_PIPE_CHUNK_FRAMES", "16")
+    if pipeline == "small_ring":
+        # a pipeline chunk is 16 frames x 416 atoms x 24 bytes = 159 744 bytes: in ring chunks of 9 KB that is 17.3, so 18
+        # chunks on 16 slots with a partial tail
+        piece, ring_chunk = 16 * frames.shape[1] * 24, 9 * 1024
+        assert piece > 16 * ring_chunk and piece % ring_chunk != 0
+        monkeypatch.setenv("SITATOR_RING_CHUNK_KB", "9")
 
     def run(width):
         monkeypatch.setenv("SITATOR_ROW_WIDTH", width)

@@ -424,3 +424,42 @@ def test_occupancy_check_first_offender_and_statistics(oracle, F, M, max_per_sit
 def test_site_counts(F, M):
     lab, K = make_labels(F, M, seed=F * 1000 + M)
     assert np.array_equal(_ctx(lab).site_counts(K), np.bincount(lab[lab >= 0], minlength=K))
+
+
+# ---- the staged copies of labels and positions (transfer.hip), at a size that goes round the ring --------------------------
+
+@pytest.fixture
+def small_ring(monkeypatch):
+    """Ring chunks of 64 KB and every read-back staged: a copy of a megabyte laps the 16 slots."""
+    monkeypatch.setenv("SITATOR_RING_CHUNK_KB", "64")
+    monkeypatch.setenv("SITATOR_STAGED_D2H_MB", "0")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("F,M", [(601, 256), (3, 5)])
+def test_labels_and_confidences_read_back_bit_for_bit(small_ring, F, M):
+    """[601, 256]: 1 230 848 bytes per array = 19 chunks of 64 KB, more than one lap, the last one partial; [3, 5] is
+    the control below one chunk."""
+    rng = np.random.default_rng(F)
+    lab = rng.integers(-1, 50, size=(F, M))
+    lab[0, 0] = lab[-1, -1] = -1
+    conf = rng.uniform(size=(F, M))
+    c = _ctx(lab)
+    c.set_assignments(lab, conf)
+    got_lab, got_conf, _ = c.assignments()
+    assert np.array_equal(got_lab.reshape(F, M), lab)
+    assert np.array_equal(got_conf.view(np.uint64).reshape(F, M), conf.view(np.uint64))
+    c.close()
+
+
+@pytest.mark.gpu
+def test_host_positions_pass_through_the_clamp_bit_for_bit(small_ring):
+    """Every role -1 and no wrapping: the output is the input.  [601, 100, 3] is 1 442 400 bytes = 23 chunks of 64 KB, up
+    through copy_to_device and back through the staged copy_to_host."""
+    F, M, A = 601, 256, 100
+    rng = np.random.default_rng(7)
+    c = _ctx(rng.integers(-1, 50, size=(F, M)))
+    pos = rng.normal(scale=20.0, size=(F, A, 3))
+    out = c.clamp_trajectory(np.full(A, -1), np.zeros((A, 3)), np.zeros((0, 3)), False, False, positions=pos)
+    assert np.array_equal(out.view(np.uint64), pos.view(np.uint64))
+    c.close()
