@@ -70,7 +70,7 @@ const char *sit_last_message(sit_ctx *ctx);
  * frame), out[5] = bytes of a communicator id (sit_comm_unique_id).  Writes min(n, 6) words and returns 6.  A binding
  * checks its own struct declarations against these once, at import (tests/test_abi.py does it for the ctypes stubs of
  * INTEGRATION.md and sitator_amd/_lib.py).  No context, no GPU needed.                                        */
-#define SIT_ABI_VERSION 5
+#define SIT_ABI_VERSION 6
 int sit_abi(int32_t *out, int n);
 /* Device buffers of 1 MB and more (the trajectory, the landmark rows, labels, the fit's arena) are kept by the process
  * when a context lets go of them, up to as much as its contexts have held at once, and handed to the next context that asks for a similar size: a process
@@ -363,6 +363,49 @@ int sit_speed_spectrum(sit_ctx *ctx, const double *positions, int64_t F, const i
 int sit_clamp_trajectory(sit_ctx *ctx, const double *positions, int64_t F, int64_t A, const int32_t *role,
                          const double *fixed_pos, const double *centers, int64_t K, int wrap,
                          int pass_through_unassigned, int64_t workspace_bytes, double *out, int64_t *first_unassigned);
+
+/* ---- per-site point clouds (SiteTrajectory.real_positions_for_site, SiteTrajectory.py:160-184, for all sites at once) ---- */
+
+/* A stable grouping of the assigned entries of the resident labels [F, M] by site.  Entry e = frame * M + column with
+ * label s >= 0 belongs to site s; the grouped order is sites ascending and, inside a site, ascending e: the order of
+ * real_traj[:, mobile_mask][traj == s].  Entries with label -1 are left out.  Per grouped element the context keeps the
+ * position (three doubles copied bit for bit), the confidence and e; offsets[K + 1] comes back (offsets[s + 1] - offsets[s]
+ * is what sit_site_counts returns).  positions: host [F, A, 3] of which mobile_idx [M] names the label columns' atoms,
+ * staged in chunks of frames that fit workspace_bytes (0: 1 GiB; a cap below one frame is SIT_ERR_INVALID); or NULL for
+ * the frames resident after sit_set_frames / sit_upload_fill_fit with the context's own mobile columns (mobile_idx is not
+ * looked at).  A counting sort in three passes (histogram per chunk of entries, scan, scatter; csrc/group_plan.h); the rank
+ * of an entry among equal labels comes from the entry order, so two ions on one site in one frame keep their order.
+ * Every label is looked at before anything is indexed with it: a label >= K fails like sit_jump_analysis (SIT_ERR_INVALID,
+ * message starting "index ", IndexError in Python), a label < -1, an F, A or M other than the resident ones with
+ * SIT_ERR_INVALID; more than 2^31 entries with SIT_ERR_CAPACITY.  Reads only: labels, rows, frames and their validity stay
+ * as they are.  The grouping stays in the context until the next call or sit_destroy and is tied to the labels it was made
+ * from: once they are rewritten (sit_predict, sit_fill with assign, sit_set_assignments, sit_assign_last_known, new frames)
+ * the sit_grouped_* calls fail with SIT_ERR_INVALID and a message starting "stale".                                   */
+int sit_group_by_site(sit_ctx *ctx, const double *positions, int64_t F, int64_t A, const int64_t *mobile_idx, int64_t M,
+                      int64_t K, int64_t workspace_bytes, int64_t *offsets);
+/* Elements [first, first + n) of the grouping: pts [n, 3], confs [n], entries [n]; each may be NULL.              */
+int sit_grouped_fetch(sit_ctx *ctx, int64_t first, int64_t n, double *pts, double *confs, int64_t *entries);
+/* NAvgsPerSite (misc/NAvgsPerSite.py:55-62): centers_out[(s * n_avg + i), 3] = PBCCalculator.average (util/PBCCalculator.pyx:
+ * 106-139) of the elements of site s at ranks i, i + n_avg, ... - weighted by their confidences, the anchor being the
+ * first element of maximal weight, or unweighted, the anchor being the first element.  The shifted and wrapped points are
+ * the reference's bit for bit; they are summed per thread in index order and then by a fixed tree of 256, so a bucket's
+ * result depends on its own elements only.  Sites with at most n_avg elements are not averaged: NaN.  anchors_out
+ * (optional) [K * n_avg]: the grouped index of every bucket's anchor, -1 where not averaged.                       */
+int sit_grouped_bucket_averages(sit_ctx *ctx, int64_t n_avg, int weighted, double *centers_out, int64_t *anchors_out);
+/* Step i of SiteVolumes.compute_accessable_volumes' recentring (site_descriptors/SiteVolumes.py:58-62) for all sites at
+ * once, on a working copy of the grouped positions that step 0 makes: per site offset = centroid - copy[anchor], anchor =
+ * (int64)((double)i * ((double)len / (double)n_recenterings)), then copy += offset and wrap_points - cumulative, as the
+ * reference works in place.  Steps come in order from 0.  pts_out (optional) [N, 3]: the copy after the step, bit-equal
+ * to the reference's array.  A site without elements fails as the reference's pos[0] does (SIT_ERR_INVALID, message
+ * starting "index ", IndexError in Python).                                                                          */
+int sit_grouped_recenter_step(sit_ctx *ctx, int64_t i, int64_t n_recenterings, double *pts_out);
+/* The plan for n_entries entries and K sites, no context needed: out4 = {entries per chunk, chunks, 1 if a chunk's
+ * per-site cursors are kept in LDS, the largest K for which they are}.                                              */
+int sit_group_plan(int64_t n_entries, int64_t K, int64_t *out4);
+/* Of the context's last grouping: [0] grouped elements, [1] K, [2] chunks, [3] LDS form, and device time (ms, HIP events)
+ * of the last [4] sit_group_by_site (from its first kernel to its last, the host's part in between included),
+ * [5] bucket-average kernel, [6] pair of recentring kernels.                                                        */
+int sit_group_info(sit_ctx *ctx, double *out, int n);
 
 /* ---- frame sharding across GPUs ------------------------------------ */
 

@@ -9,7 +9,7 @@ Host code is Python and talks to hand-written HIP kernels (gfx950) through the c
 from .errors import (InsufficientSitesError, LandmarkAnalysisError, MultipleOccupancyError,  # noqa: F401
                      StaticLatticeError, ZeroLandmarkError)
 from .site_network import SiteNetwork, Structure  # noqa: F401
-from .site_trajectory import SiteTrajectory  # noqa: F401
+from .site_trajectory import SiteGrouping, SiteTrajectory  # noqa: F401
 from .pbc import PBCCalculator  # noqa: F401
 from .dotprod_classifier import DotProdClassifier, LandmarkVectors  # noqa: F401
 from .landmark import LandmarkAnalysis  # noqa: F401
@@ -17,5 +17,7 @@ from .dynamics import (AverageVibrationalFrequency, GenerateClampedTrajectory, J
                        MergeSitesByThreshold, RemoveUnoccupiedSites, ReplaceUnassignedPositions, SmoothSiteTrajectory)
 from .merging import MergeSites, MergeSitesError, MergedSitesTooDistantError  # noqa: F401
 from .recenter import RecenterTrajectory  # noqa: F401
+from .misc import NAvgsPerSite  # noqa: F401
+from .site_descriptors import InsufficientCoordinatingAtomsError, SiteVolumes  # noqa: F401
 
 __version__ = "0.1.0"

@@ -40,7 +40,7 @@ class FillParams(C.Structure):
                    int(store_rows), int(assign), int(predict_normed), int(defer), float(predict_threshold))
 
 
-ABI_VERSION = 5          # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
+ABI_VERSION = 6          # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
 
 
 # every symbol include/sitator_hip.h declares: (restype, argtypes)
@@ -102,6 +102,12 @@ SIGNATURES = {
     "sit_recenter": (C.c_int, [_vp, _dp, i64, i64, _dp, _dp, _dp]),
     "sit_speed_spectrum": (C.c_int, [_vp, _dp, i64, _ip, i64, _dp, _u8p, i64, _dp, _dp, _dp, _dp]),
     "sit_clamp_trajectory": (C.c_int, [_vp, _dp, i64, i64, _i32p, _dp, _dp, i64, C.c_int, C.c_int, i64, _dp, _ip]),
+    "sit_group_by_site": (C.c_int, [_vp, _dp, i64, i64, _ip, i64, i64, i64, _ip]),
+    "sit_grouped_fetch": (C.c_int, [_vp, i64, i64, _dp, _dp, _ip]),
+    "sit_grouped_bucket_averages": (C.c_int, [_vp, i64, C.c_int, _dp, _ip]),
+    "sit_grouped_recenter_step": (C.c_int, [_vp, i64, i64, _dp]),
+    "sit_group_plan": (C.c_int, [i64, i64, _ip]),
+    "sit_group_info": (C.c_int, [_vp, _dp, C.c_int]),
     "sit_comm_unique_id": (C.c_int, [_u8p]),
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
     "sit_comm_destroy": (C.c_int, [_vp]),
@@ -158,6 +164,14 @@ def device_count():
     return n.value
 
 
+def group_plan(n_entries, K):
+    """``(entries per chunk, chunks, LDS form, largest K of the LDS form)`` of ``group_by_site`` (``sit_group_plan``)."""
+    out = np.zeros(4, dtype=np.int64)
+    if load().sit_group_plan(int(n_entries), int(K), _i(out)) != OK:
+        raise ValueError("group_plan: beyond the capacity of group_by_site")
+    return int(out[0]), int(out[1]), bool(out[2]), int(out[3])
+
+
 def release_cached_memory():
     """Returns the idle large device buffers the library keeps between contexts (sit_release_cached_memory)."""
     load().sit_release_cached_memory()
@@ -199,7 +213,7 @@ class HipContext(object):
             msg = self.message()
             self.close()
             raise RuntimeError("sit_create failed on device %d: %s (is a GPU visible?)" % (device, msg))
-        self.D = self.S = self.M = self.F = self.N = self.K = 0
+        self.D = self.S = self.M = self.F = self.N = self.K = self.A = 0
         self.frame0 = 0
         # who may trust the resident labels (site_trajectory.py): a counter of their rewrites and, when somebody has
         # looked, (version, content digest) of what is there
@@ -763,6 +777,67 @@ class HipContext(object):
         self._check(rc)
         return out
 
+    # -- per-site point clouds: reads labels and frames only (labels_version, rows and labels stay)
+    def _check_index(self, rc):
+        if rc == E_INVALID and self.message().startswith("index "):
+            raise IndexError(self.message())
+        self._check(rc)
+
+    def group_by_site(self, K, positions=None, mobile_idx=None, workspace_bytes=0):
+        """``offsets`` int64 ``[K + 1]`` of a stable grouping of the assigned entries ``frame * M + column`` of the resident
+        labels by site (``sit_group_by_site``): sites ascending, entries ascending inside a site - the order of
+        ``real_traj[:, mobile_mask][traj == site]``.  ``positions``: a host ``[F, A, 3]`` float64 array with ``mobile_idx``
+        ``[M]`` naming the atoms of the label columns; without it the frames resident after ``set_frames`` are read.  The
+        grouping stays on the device (``grouped_fetch``, ``grouped_bucket_averages``, ``grouped_recenter_step``) until the
+        labels are rewritten.  A label ``>= K`` raises ``IndexError``, anything else that does not fit ``ValueError``."""
+        K = int(K)
+        offsets = np.zeros(K + 1, dtype=np.int64)
+        if positions is not None:
+            positions = _f64(positions)
+            assert positions.ndim == 3 and positions.shape[2] == 3
+            midx = _i64(mobile_idx).reshape(-1)
+            F, A, M = positions.shape[0], positions.shape[1], len(midx)
+        else:
+            midx = None
+            F, A, M = self.F, self.A, self.M
+        rc = self.lib.sit_group_by_site(self._h, None if positions is None else _d(positions), int(F), int(A),
+                                        None if midx is None else _i(midx), int(M), K, int(workspace_bytes), _i(offsets))
+        self._check_index(rc)
+        return offsets
+
+    def grouped_fetch(self, first, n, points=True, confidences=False, entries=False):
+        """``(points [n, 3], confidences [n], entries [n])`` of the elements ``[first, first + n)`` of the grouping, ``None``
+        for what was not asked for.  ``ValueError`` ("stale ...") once the labels have been rewritten."""
+        n = int(n)
+        pts = np.empty((n, 3)) if points else None
+        cf = np.empty(n) if confidences else None
+        en = np.empty(n, dtype=np.int64) if entries else None
+        self._check(self.lib.sit_grouped_fetch(self._h, int(first), n, None if pts is None else _d(pts),
+                                               None if cf is None else _d(cf), None if en is None else _i(en)))
+        return pts, cf, en
+
+    def grouped_bucket_averages(self, K, n_avg, weighted):
+        """``(centers [K, n_avg, 3], anchors [K, n_avg])``: ``PBCCalculator.average`` of the elements of every site at ranks
+        ``i, i + n_avg, ...`` (``sit_grouped_bucket_averages``); NaN / -1 for sites of at most ``n_avg`` elements."""
+        out = np.empty((int(K), int(n_avg), 3))
+        anchors = np.empty((int(K), int(n_avg)), dtype=np.int64)
+        self._check(self.lib.sit_grouped_bucket_averages(self._h, int(n_avg), int(bool(weighted)), _d(out), _i(anchors)))
+        return out, anchors
+
+    def grouped_recenter_step(self, i, n_recenterings, out):
+        """Step ``i`` of the cumulative recentring of every site's points (``sit_grouped_recenter_step``) into ``out``
+        ``[N, 3]`` (float64, C-contiguous; ``None``: not copied back).  An empty site raises ``IndexError``."""
+        if out is not None:
+            assert out.dtype == np.float64 and out.flags.c_contiguous and out.ndim == 2 and out.shape[1] == 3
+        self._check_index(self.lib.sit_grouped_recenter_step(self._h, int(i), int(n_recenterings), None if out is None else _d(out)))
+        return out
+
+    def group_info(self):
+        v = np.zeros(7)
+        self.lib.sit_group_info(self._h, _d(v), 7)
+        return {"n_grouped": int(v[0]), "n_sites": int(v[1]), "chunks": int(v[2]), "lds": bool(v[3]), "group_ms": float(v[4]),
+                "bucket_avg_ms": float(v[5]), "recenter_ms": float(v[6])}
+
     # ---- RCCL exchange of the frame-sharded path (csrc/comm.hip) ----
     def comm_create(self, unique_id, rank, world):
         uid = np.frombuffer(bytes(unique_id), dtype=np.uint8).copy()
@@ -868,6 +943,7 @@ for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "a
               "gram_limbs", "weighted_row_sums", "weighted_row_sums_limbs", "best_match", "best_match_groups",
               "site_anchors", "site_sums", "check_occupancy", "site_counts", "cooccupancy", "jump_sources", "jump_list",
               "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
-              "unknown_runs", "replace_closer", "clamp_trajectory"):
+              "unknown_runs", "replace_closer", "clamp_trajectory", "group_by_site", "grouped_fetch", "grouped_bucket_averages",
+              "grouped_recenter_step"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

@@ -483,7 +483,7 @@ extern "C" int sit_set_centers(sit_ctx *c, const double *centers, i64 K, int nor
     for (i64 d = 0; d < D; d++) if (ptr[(size_t)d + 1] - ptr[(size_t)d] > c->max_col) c->max_col = ptr[(size_t)d + 1] - ptr[(size_t)d];
     if ((rc = dev_alloc(c, &c->d_counts, K))) return rc;
     if ((rc = dev_upload(c, &c->d_cen_dense, centers, K * D))) return rc;   // dense fallback
-    c->assign_valid = false;
+    c->assign_valid = false; c->labels_gen++;
     return SIT_OK;
 }
 
@@ -571,7 +571,7 @@ static int run_predict(sit_ctx *c, double threshold, bool words_reset = false)
     }
     if (c->N == 0) {
         HIP_TRY(c, hipMemsetAsync(c->d_counts, 0, sizeof(i64) * (size_t)c->K, c->stream));
-        c->assign_valid = true;
+        c->assign_valid = true; c->labels_gen++;
         return SIT_OK;
     }
     PredArgs a;
@@ -600,7 +600,7 @@ static int run_predict(sit_ctx *c, double threshold, bool words_reset = false)
     HIP_TRY(c, hipGetLastError());
     if (!counted && (rc = sit_label_counts(c))) return rc;      // np.bincount(labels[labels >= 0]) (:92)
     t.stop();
-    c->assign_valid = true;
+    c->assign_valid = true; c->labels_gen++;
     return SIT_OK;
 }
 
@@ -623,7 +623,7 @@ int predict_listed_rows(sit_ctx *c, double threshold, i32 *wlist, unsigned *wcou
     int rc = sit_label_counts(c, false);
     if (rc) return rc;
     t.stop();
-    c->assign_valid = true;
+    c->assign_valid = true; c->labels_gen++;
     return SIT_OK;
 }
 
@@ -1615,6 +1615,6 @@ extern "C" int sit_set_rows_dense(sit_ctx *c, const double *rows, i64 N, i64 D)
     if ((rc = dev_upload(c, &c->d_row_idx, idx.data(), N * W))) return rc;
     if ((rc = dev_upload(c, &c->d_row_val, val.data(), N * W))) return rc;
     c->D = D; c->N = N; c->rows_W = W; c->rows_N = N;
-    c->rows_valid = true; c->assign_valid = false;
+    c->rows_valid = true; c->assign_valid = false; c->labels_gen++;
     return SIT_OK;
 }

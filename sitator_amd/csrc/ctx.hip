@@ -245,6 +245,7 @@ extern "C" void sit_destroy(sit_ctx *c)
     for (void *p : ptrs) if (p) sit_dfree(c, p);
     fitfast_free(c);
     spectrum_free(c);
+    group_free(c);
     fill_ring_free(c);
     stream_give(c->device, 1, c->copy_stream);
     stream_give(c->device, 2, c->copy_stream2);
@@ -472,7 +473,7 @@ extern "C" int sit_set_basis(sit_ctx *c, const double *ref_static, i64 S, const 
     c->fill_kernel = (fk && fk[0] == '1') ? 1 : 3;
     for (void **q : {(void **)&c->d_vh, (void **)&c->d_vh16, (void **)&c->d_ref_soa, (void **)&c->d_nv}) if (*q) { sit_dfree(c, *q); *q = nullptr; }
     c->tight_valid = false;
-    c->rows_valid = false; c->assign_valid = false; c->map_valid = false;
+    c->rows_valid = false; c->assign_valid = false; c->labels_gen++; c->map_valid = false;
     return SIT_OK;
 }
 
@@ -503,7 +504,7 @@ int set_frame_meta(sit_ctx *c, i64 F, i64 A, const i64 *static_idx, i64 S, const
     for (i64 i = 1; i < M; i++) if (m32[(size_t)i] != m32[0] + (i32)i) c->idx_contig = false;
     c->idx_s0 = s32[0]; c->idx_m0 = m32[0];
     c->F = F; c->A = A; c->M = M; c->frame0 = frame0; c->N = F * M;
-    c->rows_valid = false; c->assign_valid = false; c->map_valid = false; c->tight_valid = false; c->rows_overflowed = false;
+    c->rows_valid = false; c->assign_valid = false; c->labels_gen++; c->map_valid = false; c->tight_valid = false; c->rows_overflowed = false;
     return SIT_OK;
 }
 

@@ -307,6 +307,7 @@ extern "C" int sit_assign_last_known(sit_ctx *c, i64 frame_threshold, const i64 
     if (nch > 0) k_label_chunk_summary<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, 0, s.sum);
     k_alk_chunk_carry<<<dim3((unsigned)((M + 63) / 64)), dim3(64), 0, c->stream>>>(
         F, M, nch, last_known_in ? s.in0 : nullptr, time_unknown_in ? s.in1 : nullptr, s.sum, s.carry, s.out0, s.out1);
+    c->labels_gen++;                                         // the replay rewrites the resident labels in place
     if (nch > 0) k_alk_chunk_replay<<<cgrid, dim3(64), 0, c->stream>>>(c->d_labels, F, M, frame_threshold, s.carry, d_fm, d_st);
     HIP_TRY(c, hipGetLastError());
     u64 st[3];
@@ -746,6 +747,6 @@ extern "C" int sit_recenter_resident(sit_ctx *c, const double *masses, const dou
     k_recenter<<<dim3((unsigned)c->F), dim3(256), 0, c->stream>>>(c->d_frames, A, dc, add3 ? add3[0] : 0.0, add3 ? add3[1] : 0.0, add3 ? add3[2] : 0.0);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipStreamSynchronize(c->stream));         // coef lives on this stack frame
-    c->rows_valid = false; c->assign_valid = false; c->map_valid = false; c->tight_valid = false;
+    c->rows_valid = false; c->assign_valid = false; c->labels_gen++; c->map_valid = false; c->tight_valid = false;
     return SIT_OK;
 }

@@ -531,10 +531,10 @@ static int fill_decode(sit_ctx *c, const FillPending &s, i64 *n_all_zero, sit_er
     for (int q = 0; q < 4; q++) c->census[q] = (double)s.host[5 + q];
     bool overflow;
     const int kind = decode_fill_words(c, s.host, n_all_zero, err, &overflow);
-    if (kind != SIT_OK) { c->assign_valid = false; return kind; }
+    if (kind != SIT_OK) { c->assign_valid = false; c->labels_gen++; return kind; }
     if (s.v3 && overflow) {
         if (s.rows_measured && superseded) return SIT_OK;
-        c->assign_valid = false; c->rows_valid = false;
+        c->assign_valid = false; c->labels_gen++; c->rows_valid = false;
         if (s.rows_measured) { c->rows_overflowed = true; return SIT_RETRY; }       // a row beyond the measured width: once more at the rigorous one
         c->msg = "landmark row wider than the pruning bound (internal error)";
         return SIT_ERR_CAPACITY;
@@ -686,7 +686,7 @@ extern "C" int sit_fill(sit_ctx *c, const sit_fill_params *p, i64 *n_all_zero, s
         }
         if (c->F == 0) {
             if (n_all_zero) *n_all_zero = 0;
-            c->rows_valid = store; c->assign_valid = assign;
+            c->rows_valid = store; c->assign_valid = assign; c->labels_gen++;
             if (assign) HIP_TRY(c, hipMemsetAsync(c->d_counts, 0, sizeof(i64) * (size_t)c->K, c->stream));
             return SIT_OK;
         }
@@ -702,7 +702,7 @@ extern "C" int sit_fill(sit_ctx *c, const sit_fill_params *p, i64 *n_all_zero, s
         // the assignment is enqueued behind the fill without waiting for the fill's error word (if the fill did report
         // an error the assignment is simply discarded)
         c->rows_valid = store || !fused;
-        c->assign_valid = false;
+        c->assign_valid = false; c->labels_gen++;
         if (assign) {
             if (fused) rc = predict_listed_rows(c, p->predict_threshold, c->fuse_wlist, c->fuse_wcount, c->fuse_seg_cap, c->fuse_nseg);
             else rc = sit_predict_internal(c, p->predict_threshold, pred_reset);
@@ -877,7 +877,7 @@ extern "C" int sit_upload_fill_fit(sit_ctx *c, const double *frames, i64 F, i64 
     timer.stop();
     if (dbgpipe) fprintf(stderr, "  last fit done at %.1f ms\n", since());
     c->rows_valid = true;
-    c->assign_valid = false;
+    c->assign_valid = false; c->labels_gen++;
     u64 *hb = (u64 *)c->h_pinned;
     if (hipMemcpyAsync(hb, c->d_err, 72, hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
         c->msg = "read-back of the fill's error word failed";

@@ -152,6 +152,8 @@ struct sit_ctx {
     i64 scratch_bytes = 0;
     void *fill_ring = nullptr;        // results of deferred fills not yet collected (fill.hip)
     void *spectrum = nullptr;         // tables and buffers of sit_speed_spectrum (spectrum.hip); opaque here
+    void *group = nullptr;            // the grouping of sit_group_by_site (group.hip); opaque here
+    i64 labels_gen = 0;               // counts every write of the resident labels (and every change of their validity): what a grouping is stamped with
 };
 
 #define HIP_TRY(ctx, expr)                                                              \
@@ -486,6 +488,7 @@ int predict_reset_with_fill(sit_ctx *c, bool *done);                // cluster.h
 int sit_label_counts(sit_ctx *c, bool zero = true);              // zero = false: the counts were reset by the caller
 void fitfast_free(sit_ctx *c);
 void spectrum_free(sit_ctx *c);
+void group_free(sit_ctx *c);
 bool fitfast_valid(sit_ctx *c);
 void fitfast_invalidate(sit_ctx *c);
 int fitfast_set_state(sit_ctx *c, const double *cen, const i64 *cnt, i64 K);

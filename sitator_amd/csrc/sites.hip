@@ -387,6 +387,6 @@ extern "C" int sit_set_assignments(sit_ctx *c, const i64 *labels, const double *
         else HIP_TRY(c, hipMemsetAsync(c->d_confs, 0, (size_t)c->N * 8, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    c->assign_valid = true;
+    c->assign_valid = true; c->labels_gen++;
     return SIT_OK;
 }

@@ -28,6 +28,43 @@ def _digest(arr):
     return (a.shape, hashlib.blake2b(raw, digest_size=16).digest())
 
 
+class SiteGrouping(object):
+    """The real-space positions of a ``SiteTrajectory`` grouped by site, on the device (``SiteTrajectory.group_real_positions``):
+    one stable counting sort instead of one masked copy of the whole mobile trajectory per site.
+
+    ``offsets`` (int64 ``[n_sites + 1]``), ``counts`` (``[n_sites]``, what ``compute_site_occupancies`` counts) and
+    ``n_sites`` are on the host; points are copied from the GPU site by site.  The grouping describes the labels as they
+    were when it was made: once they are rewritten on the device its methods raise ``ValueError`` ("stale ...")."""
+
+    def __init__(self, ctx, offsets, has_confidences):
+        self._ctx = ctx
+        self._has_confidences = bool(has_confidences)
+        self.offsets = offsets
+        self.counts = np.diff(offsets)
+        self.n_sites = len(offsets) - 1
+
+    def __len__(self):
+        return self.n_sites
+
+    def _range(self, site):
+        site = int(site)
+        assert 0 <= site < self.n_sites
+        return int(self.offsets[site]), int(self.counts[site])
+
+    def positions(self, site, return_confidences=False):
+        """What ``real_positions_for_site`` returns, in its order, as arrays that own their data."""
+        if return_confidences and not self._has_confidences:
+            raise ValueError("This SiteTrajectory has no confidences")
+        first, n = self._range(site)
+        pts, confs, _ = self._ctx.grouped_fetch(first, n, True, return_confidences)
+        return (pts, confs) if return_confidences else pts
+
+    def entries(self, site):
+        """``frame * n_mobile + mobile atom`` of every point of the site, ascending."""
+        first, n = self._range(site)
+        return self._ctx.grouped_fetch(first, n, False, False, True)[2]
+
+
 class SiteTrajectory(object):
     """Site assignment of every mobile particle in every frame."""
 
@@ -156,6 +193,29 @@ class SiteTrajectory(object):
         if return_confidences:
             return pts, self._confs[sel].flatten()
         return pts
+
+    def group_real_positions(self, _resident=False):
+        """A ``SiteGrouping``: the points ``real_positions_for_site`` hands out, for all sites at once and kept on the GPU
+        (``sit_group_by_site``: a stable counting sort of the assigned (frame, atom) entries by site).  Raises
+        ``ValueError`` without a real trajectory or for one that is not float64, ``IndexError`` for a label beyond the
+        sites, ``NotImplementedError`` on a frame shard.  ``_resident``: read the frames a ``LandmarkAnalysis`` left on the
+        device this trajectory shares instead of ``real_trajectory``."""
+        if self._comm is not None and self._comm.size > 1:
+            raise NotImplementedError("group_real_positions needs all frames of the trajectory on one GPU; this "
+                                      "trajectory is a frame shard")
+        n_sites = int(self._sn.n_sites)
+        if _resident:
+            ctx = self._device()
+            offsets = ctx.group_by_site(n_sites)
+        else:
+            if self._real_traj is None:
+                raise ValueError("This SiteTrajectory has no real trajectory")
+            real = np.asarray(self._real_traj)
+            if real.dtype != np.float64:
+                raise ValueError("Buffer dtype mismatch, expected 'double' but got '%s'" % real.dtype)
+            ctx = self._device()
+            offsets = ctx.group_by_site(n_sites, positions=real, mobile_idx=np.where(self._sn.mobile_mask)[0])
+        return SiteGrouping(ctx, offsets, self._confs is not None)
 
     def compute_site_occupancies(self):
         """Occupancy of every site: assignments to it divided by the number of frames (above 1 possible under multiple
