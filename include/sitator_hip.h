@@ -70,7 +70,7 @@ const char *sit_last_message(sit_ctx *ctx);
  * frame), out[5] = bytes of a communicator id (sit_comm_unique_id).  Writes min(n, 6) words and returns 6.  A binding
  * checks its own struct declarations against these once, at import (tests/test_abi.py does it for the ctypes stubs of
  * INTEGRATION.md and sitator_amd/_lib.py).  No context, no GPU needed.                                        */
-#define SIT_ABI_VERSION 6
+#define SIT_ABI_VERSION 7
 int sit_abi(int32_t *out, int n);
 /* Device buffers of 1 MB and more (the trajectory, the landmark rows, labels, the fit's arena) are kept by the process
  * when a context lets go of them, up to as much as its contexts have held at once, and handed to the next context that asks for a similar size: a process
@@ -455,6 +455,16 @@ int sit_timers(sit_ctx *ctx, double *ms, int n);
  * (ion, slot of its candidate list)) and the widest slots per ion a window of that launch could take (8: every list fits
  * eight slots; 16 / 32 / 64: a frame that meets a longer list runs that many slots per ion).                 */
 int sit_info(sit_ctx *ctx, double *out, int n);
+/* Diagnostic read-back of a pruning table as it lies on the device (which = 0: the loose table of sit_set_basis, 1: the
+ * tight table the first sit_fill over the frames of a basis builds).  Always written (each may be NULL): G3[3] the grid,
+ * *displacement the static displacement the table was built for, *rb the covering radius of a bin it was built with,
+ * *total its entries.  off [G3[0] * G3[1] * G3[2] + 1] (bin (x, y, z) is index (x * G3[1] + y) * G3[2] + z), list [total]
+ * the landmarks of every bin, ascending, and crit [total] the critical vertex of every entry are copied when given
+ * (list_cap counts the elements of list and of crit); a call with all three NULL sizes the second.  SIT_ERR_INVALID with
+ * a message: no basis, a capacity too small, or that table does not exist (a tight table is dropped by sit_set_basis
+ * and by new frames).  Not part of any hot path (tests/test_gpu_candidates.py).                              */
+int sit_candidate_table(sit_ctx *ctx, int which, int32_t *G3, double *displacement, double *rb, int64_t *total,
+                        int64_t off_cap, int32_t *off, int64_t list_cap, int32_t *list, uint8_t *crit);
 int sit_synchronize(sit_ctx *ctx);
 
 #ifdef __cplusplus

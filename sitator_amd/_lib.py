@@ -40,7 +40,7 @@ class FillParams(C.Structure):
                    int(store_rows), int(assign), int(predict_normed), int(defer), float(predict_threshold))
 
 
-ABI_VERSION = 6          # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
+ABI_VERSION = 7          # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
 
 
 # every symbol include/sitator_hip.h declares: (restype, argtypes)
@@ -119,6 +119,7 @@ SIGNATURES = {
     "sit_comm_attach": (C.c_int, [_vp, _vp]),
     "sit_timers": (C.c_int, [_vp, _dp, C.c_int]),
     "sit_info": (C.c_int, [_vp, _dp, C.c_int]),
+    "sit_candidate_table": (C.c_int, [_vp, C.c_int, _i32p, _dp, _dp, _ip, i64, _i32p, i64, _i32p, _u8p]),
     "sit_synchronize": (C.c_int, [_vp]),
 }
 
@@ -919,6 +920,23 @@ class HipContext(object):
         out["census"] = [float(x) for x in v[24:28]]
         out["fill_slot_width"] = int(v[28])
         return out
+
+    def candidate_table(self, which):
+        """The pruning table as it lies on the device (``sit_candidate_table``; diagnostic): ``which`` 0 = the loose table of
+        ``set_basis``, 1 = the tight table of the first ``fill``.  A dict of ``grid`` [3], ``displacement``, ``rb``, ``total``,
+        ``off`` int32 [bins + 1], ``list`` int32 [total], ``crit`` uint8 [total].  ``ValueError`` when there is no such table."""
+        G = np.zeros(3, dtype=np.int32)
+        disp, rb, total = C.c_double(0), C.c_double(0), i64(0)
+        head = (self._h, int(which), G.ctypes.data_as(_i32p), C.byref(disp), C.byref(rb), C.byref(total))
+        self._check(self.lib.sit_candidate_table(*head, 0, None, 0, None, None))
+        nb, n = int(G[0]) * int(G[1]) * int(G[2]), int(total.value)
+        off = np.zeros(nb + 1, dtype=np.int32)
+        lst = np.zeros(max(n, 1), dtype=np.int32)
+        crit = np.zeros(max(n, 1), dtype=np.uint8)
+        self._check(self.lib.sit_candidate_table(*head, nb + 1, off.ctypes.data_as(_i32p), len(lst), lst.ctypes.data_as(_i32p),
+                                                 crit.ctypes.data_as(_u8p)))
+        return {"grid": [int(x) for x in G], "displacement": disp.value, "rb": rb.value, "total": n, "off": off,
+                "list": lst[:n], "crit": crit[:n]}
 
     def synchronize(self):
         self._check(self.lib.sit_synchronize(self._h))

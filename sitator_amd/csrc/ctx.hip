@@ -464,7 +464,7 @@ extern "C" int sit_set_basis(sit_ctx *c, const double *ref_static, i64 S, const 
     if ((rc = dev_upload(c, &c->d_verts, v32.data(), D * Vp))) return rc;
     if ((rc = dev_upload(c, &c->d_vcd, vcdp.data(), D * Vp))) return rc;
     // loose table: valid for any frame the static-lattice check accepts (displacement <= static_thr), 1 A bins
-    if ((rc = sit_build_candidates(c, static_thr, 1.0, &c->d_bin_off, &c->d_bin_list, &c->d_bin_crit, c->G, &c->W, &c->mean_candidates))) return rc;
+    if ((rc = sit_build_candidates(c, static_thr, 1.0, &c->d_bin_off, &c->d_bin_list, &c->d_bin_crit, c->G, &c->W, &c->mean_candidates, &c->cand_meta[0]))) return rc;
     c->cell_diagonal = true;
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++)

@@ -329,7 +329,7 @@ static int ensure_tight_table(sit_ctx *c)
     double delta = mx * 1.15 + 0.02;
     if (delta > c->static_thr) delta = c->static_thr;
     static const double tight_bin = [] { const char *v = getenv("SITATOR_TIGHT_BIN"); const double x = v ? atof(v) : 0.0; return x >= 0.1 && x <= 2.0 ? x : 0.5; }();
-    if ((rc = sit_build_candidates(c, delta, tight_bin, &c->d_tbin_off, &c->d_tbin_list, &c->d_tbin_crit, c->tG, &c->W_tight, &c->tight_mean_candidates))) return rc;
+    if ((rc = sit_build_candidates(c, delta, tight_bin, &c->d_tbin_off, &c->d_tbin_list, &c->d_tbin_crit, c->tG, &c->W_tight, &c->tight_mean_candidates, &c->cand_meta[1]))) return rc;
     if (c->W_tight > 255) delta = -1.0;     // the kernel keeps a list length in eight bits: loose table for everything
     c->tight_delta = delta;
     c->tight_valid = true;

@@ -25,6 +25,13 @@ struct Pbc {
 
 enum { T_FILL = 0, T_FIT = 1, T_PREDICT = 2, T_GRAM = 3, T_CENTERS = 4, T_OCC = 5, T_H2D = 6, T_CLAMP = 7, T_N = 8 };
 
+// what sit_candidate_table reports about a built pruning table (candidates.hip)
+struct CandMeta {
+    double displacement = 0, rb = 0;
+    i64 total = 0;
+    bool valid = false;               // false while a build is under way or after one that failed
+};
+
 #define SIT_NO_ERROR_KEY 0xFFFFFFFFFFFFFFFFull
 
 struct sit_ctx {
@@ -53,6 +60,7 @@ struct sit_ctx {
     i32 *d_bin_list = nullptr;
     unsigned char *d_bin_crit = nullptr, *d_tbin_crit = nullptr;   // critical vertex of every list entry (candidates.hip)
     i64 W = 0;                        // row width = longest candidate list (loose table)
+    CandMeta cand_meta[2];            // displacement, covering radius and entries of the loose [0] and the tight [1] table
     double mean_candidates = 0;
     // tight table: built for the static displacement actually present (fill.hip ensure_tight_table)
     int tG[3] = {1, 1, 1};
@@ -498,7 +506,7 @@ int fitfast_stream(sit_ctx *c, const i32 *nnz, const i32 *idx, const double *val
                    int width, i64 nrows, double threshold, i64 *consumed);
 // pruning table for static displacements up to `displacement`, built and kept on the device (candidates.hip)
 int sit_build_candidates(sit_ctx *c, double displacement, double bin_target, i32 **d_off, i32 **d_list,
-                         unsigned char **d_crit, int G_out[3], i64 *W, double *mean);
+                         unsigned char **d_crit, int G_out[3], i64 *W, double *mean, CandMeta *meta);
 bool fill3_eligible(sit_ctx *c);
 // frames [f_lo, f_hi); fuse: assign the narrow rows in the same kernel (needs centres; *fused says whether it did - if
 // not, the rows were stored whatever `store` says and the caller runs the assignment kernels)
