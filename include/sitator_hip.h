@@ -70,7 +70,7 @@ const char *sit_last_message(sit_ctx *ctx);
  * frame), out[5] = bytes of a communicator id (sit_comm_unique_id).  Writes min(n, 6) words and returns 6.  A binding
  * checks its own struct declarations against these once, at import (tests/test_abi.py does it for the ctypes stubs of
  * INTEGRATION.md and sitator_amd/_lib.py).  No context, no GPU needed.                                        */
-#define SIT_ABI_VERSION 7
+#define SIT_ABI_VERSION 8
 int sit_abi(int32_t *out, int n);
 /* Device buffers of 1 MB and more (the trajectory, the landmark rows, labels, the fit's arena) are kept by the process
  * when a context lets go of them, up to as much as its contexts have held at once, and handed to the next context that asks for a similar size: a process
@@ -88,6 +88,12 @@ int sit_wrap_points(sit_ctx *ctx, double *pts, int64_t n);
 int sit_distances(sit_ctx *ctx, const double *pt1, const double *pts2, int64_t n, double *out);
 /* PBCCalculator.average, util/PBCCalculator.pyx:106-139; weights may be NULL.        */
 int sit_average(sit_ctx *ctx, const double *pts, const double *weights, int64_t n, double *out3);
+
+/* PBCCalculator.min_image, util/PBCCalculator.pyx:262-316, for n pairs: pts[p] (in place, host buffer) becomes the one of its
+ * 27 periodic images nearest ref[p] - the first strictly smaller distance in the order of the reference's loops, its sums
+ * left to right - and code[p] = 100 i + 10 j + k names it (111: the point stayed).  Both points of a pair are taken to lie
+ * in the same cell, as in the reference.                                                */
+int sit_min_image(sit_ctx *ctx, const double *ref, double *pts, int64_t n, int32_t *code);
 
 /* LandmarkAnalysis.run Step 1 in one call (landmark/LandmarkAnalysis.py:194-202): out[k,h] =
  * PBCCalculator.distances(centers[k], ref_static[verts[k,h]]), NaN where verts[k,h] == -1.          */
@@ -406,6 +412,25 @@ int sit_group_plan(int64_t n_entries, int64_t K, int64_t *out4);
  * of the last [4] sit_group_by_site (from its first kernel to its last, the host's part in between included),
  * [5] bucket-average kernel, [6] pair of recentring kernels.                                                        */
 int sit_group_info(sit_ctx *ctx, double *out, int n);
+
+/* ---- the site graph under periodic boundaries (network/DiffusionPathwayAnalysis.py) ------------------------------------ */
+
+/* Connected components of the site graph of conn[K, K] (conn[from * K + to] != 0: connected; the reference's thresholded
+ * n_ij, :71) with centers[K, 3], for n_images = 27 of the 3 x 3 x 3 supercell graph of _build_mic_connmat (:175-228), for
+ * n_images = 1 of the plain K-node graph (true_periodic_pathways = False).  code[K, K] (optional, NULL): per connected
+ * pair 100 i + 10 j + k of min_image(centers[from], centers[to]) as sit_min_image gives it, 0 elsewhere.  Node = image * K +
+ * site, the images in the order of itertools.product(range(-1, 2), repeat = 3) (home image: 13); an edge with code 111
+ * stays inside every image, any other goes from image s to s + (digits - 1) and is dropped where that leaves [-1, 1]
+ * (:218-224).  Edges are undirected for the components (weak connection, :76-78).  root[n_images * K]: per node the LOWEST
+ * node index of its component - ranking the distinct values gives scipy's component numbers.  The labelling hooks roots
+ * with atomic minima and compresses by pointer jumping in rounds of ordinary launches (csrc/pathway_graph.h); its fixed
+ * point does not depend on the order of arrival, so the result is the same on every call.  *rounds: rounds taken, the
+ * last of which changed nothing (0 without a connected pair).  SIT_ERR_INVALID: a missing array, K < 0, K > 16384 (the mask
+ * is K * K bytes and the codes 4 K * K on the device), n_images other than 1 or 27; SIT_ERR_CAPACITY: no fixed point within
+ * n_images * K rounds (cannot happen: every round before the last lowers a label).  Reads nothing of the context but its
+ * cell: frames, rows, labels and their validity stay as they are.                                          */
+int sit_pathway_components(sit_ctx *ctx, int64_t K, const uint8_t *conn, const double *centers, int n_images,
+                           int32_t *code, int32_t *root, int64_t *rounds);
 
 /* ---- frame sharding across GPUs ------------------------------------ */
 

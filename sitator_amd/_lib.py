@@ -40,7 +40,7 @@ class FillParams(C.Structure):
                    int(store_rows), int(assign), int(predict_normed), int(defer), float(predict_threshold))
 
 
-ABI_VERSION = 7          # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
+ABI_VERSION = 8          # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
 
 
 # every symbol include/sitator_hip.h declares: (restype, argtypes)
@@ -54,6 +54,7 @@ SIGNATURES = {
     "sit_wrap_points": (C.c_int, [_vp, _dp, i64]),
     "sit_distances": (C.c_int, [_vp, _dp, _dp, i64, _dp]),
     "sit_average": (C.c_int, [_vp, _dp, _dp, i64, _dp]),
+    "sit_min_image": (C.c_int, [_vp, _dp, _dp, i64, _i32p]),
     "sit_site_vertex_distances": (C.c_int, [_vp, _dp, _dp, _ip, i64, i64, i64, _dp]),
     "sit_set_basis": (C.c_int, [_vp, _dp, i64, _ip, _dp, i64, i64, C.c_double, C.c_double, C.c_double]),
     "sit_set_frames": (C.c_int, [_vp, _dp, i64, i64, _ip, i64, _ip, i64, i64]),
@@ -108,6 +109,7 @@ SIGNATURES = {
     "sit_grouped_recenter_step": (C.c_int, [_vp, i64, i64, _dp]),
     "sit_group_plan": (C.c_int, [i64, i64, _ip]),
     "sit_group_info": (C.c_int, [_vp, _dp, C.c_int]),
+    "sit_pathway_components": (C.c_int, [_vp, i64, _u8p, _dp, C.c_int, _i32p, _i32p, _ip]),
     "sit_comm_unique_id": (C.c_int, [_u8p]),
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
     "sit_comm_destroy": (C.c_int, [_vp]),
@@ -273,6 +275,16 @@ class HipContext(object):
         out = np.empty(3)
         self._check(self.lib.sit_average(self._h, _d(pts), None if w is None else _d(w), len(pts), _d(out)))
         return out
+
+    def min_image(self, ref, pts):
+        """``(moved points [n, 3], codes int32 [n])``: every ``pts[p]`` moved to its periodic image nearest ``ref[p]`` and
+        the reference's code ``100 i + 10 j + k`` of that image (``sit_min_image``)."""
+        ref = _f64(ref).reshape(-1, 3)
+        pts = np.array(pts, dtype=np.float64).reshape(-1, 3)
+        assert ref.shape == pts.shape
+        code = np.zeros(len(pts), dtype=np.int32)
+        self._check(self.lib.sit_min_image(self._h, _d(ref), _d(pts), len(pts), code.ctypes.data_as(_i32p)))
+        return pts, code
 
     def site_vertex_distances(self, centers, ref_static, verts):
         centers = _f64(centers); ref_static = _f64(ref_static); verts = _i64(verts)
@@ -839,6 +851,25 @@ class HipContext(object):
         return {"n_grouped": int(v[0]), "n_sites": int(v[1]), "chunks": int(v[2]), "lds": bool(v[3]), "group_ms": float(v[4]),
                 "bucket_avg_ms": float(v[5]), "recenter_ms": float(v[6])}
 
+    # -- DiffusionPathwayAnalysis: reads nothing of the context but its cell
+    def pathway_components(self, conn, centers, n_images=27, codes=False):
+        """``(root int32 [n_images * K], rounds, code int32 [K, K] or None)`` of the site graph ``conn`` ``[K, K]`` (non-zero:
+        connected) under the context's cell (``sit_pathway_components``): per node ``image * K + site`` of the 3 x 3 x 3
+        supercell (``n_images`` 27; 1: the plain graph) the lowest node index of its connected component, the rounds the
+        labelling took, and with ``codes`` the image code of every connected pair.  More than 16384 sites: ``ValueError``."""
+        conn = np.ascontiguousarray(conn, dtype=np.uint8)
+        assert conn.ndim == 2 and conn.shape[0] == conn.shape[1]
+        K = conn.shape[0]
+        centers = _f64(centers).reshape(-1, 3)
+        assert len(centers) == K
+        root = np.empty(int(n_images) * K, dtype=np.int32)
+        code = np.empty((K, K), dtype=np.int32) if codes else None
+        rounds = i64(0)
+        self._check(self.lib.sit_pathway_components(self._h, K, conn.ctypes.data_as(_u8p), _d(centers), int(n_images),
+                                                    None if code is None else code.ctypes.data_as(_i32p),
+                                                    root.ctypes.data_as(_i32p), C.byref(rounds)))
+        return root, int(rounds.value), code
+
     # ---- RCCL exchange of the frame-sharded path (csrc/comm.hip) ----
     def comm_create(self, unique_id, rank, world):
         uid = np.frombuffer(bytes(unique_id), dtype=np.uint8).copy()
@@ -962,6 +993,6 @@ for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "a
               "site_anchors", "site_sums", "check_occupancy", "site_counts", "cooccupancy", "jump_sources", "jump_list",
               "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
               "unknown_runs", "replace_closer", "clamp_trajectory", "group_by_site", "grouped_fetch", "grouped_bucket_averages",
-              "grouped_recenter_step"):
+              "grouped_recenter_step", "min_image", "pathway_components"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

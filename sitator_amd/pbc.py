@@ -1,7 +1,7 @@
 """``PBCCalculator`` of the reference (``sitator/util/PBCCalculator.pyx``), evaluated by HIP
 kernels through the C-ABI.  Only the methods the landmark path calls are provided:
 ``wrap_points`` (:341-366), ``wrap_point`` (:174-193), ``distances`` (:64-103), ``average``
-(:106-139) and ``cell_centroid``.
+(:106-139), ``min_image`` (:262-316) and ``cell_centroid``.
 """
 import numpy as np
 
@@ -45,6 +45,15 @@ class PBCCalculator(object):
         """PBC-aware (optionally weighted) mean of a compact cloud of points."""
         assert points.ndim == 2 and points.shape[1] == 3
         return self._ctx.average(points, weights)
+
+    def min_image(self, ref, pt):
+        """Moves ``pt`` IN PLACE to the one of its 27 periodic images nearest ``ref`` (both taken to lie in the same cell) and
+        returns the image as the int ``100 i + 10 j + k`` (111: ``pt`` stayed), as the reference does (:262-316)."""
+        assert len(ref) == 3 and len(pt) == 3, "Points must be 3D"
+        moved, code = self._ctx.min_image(np.asarray(ref, dtype=np.float64).reshape(1, 3),
+                                          np.asarray(pt, dtype=np.float64).reshape(1, 3))
+        pt[...] = moved[0]
+        return int(code[0])
 
     def pairwise_distances(self, pts, out=None):
         """Pairwise shift-and-wrap distance matrix of ``pts`` with itself (:43-61): row i holds the distances
