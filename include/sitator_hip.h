@@ -70,7 +70,7 @@ const char *sit_last_message(sit_ctx *ctx);
  * frame), out[5] = bytes of a communicator id (sit_comm_unique_id).  Writes min(n, 6) words and returns 6.  A binding
  * checks its own struct declarations against these once, at import (tests/test_abi.py does it for the ctypes stubs of
  * INTEGRATION.md and sitator_amd/_lib.py).  No context, no GPU needed.                                        */
-#define SIT_ABI_VERSION 8
+#define SIT_ABI_VERSION 9
 int sit_abi(int32_t *out, int n);
 /* Device buffers of 1 MB and more (the trajectory, the landmark rows, labels, the fit's arena) are kept by the process
  * when a context lets go of them, up to as much as its contexts have held at once, and handed to the next context that asks for a similar size: a process
@@ -410,8 +410,25 @@ int sit_grouped_recenter_step(sit_ctx *ctx, int64_t i, int64_t n_recenterings, d
 int sit_group_plan(int64_t n_entries, int64_t K, int64_t *out4);
 /* Of the context's last grouping: [0] grouped elements, [1] K, [2] chunks, [3] LDS form, and device time (ms, HIP events)
  * of the last [4] sit_group_by_site (from its first kernel to its last, the host's part in between included),
- * [5] bucket-average kernel, [6] pair of recentring kernels.                                                        */
+ * [5] bucket-average kernel, [6] pair of recentring kernels, [7] hull kernel (sit_grouped_hull_volumes).              */
 int sit_group_info(sit_ctx *ctx, double *out, int n);
+/* Convex hulls of every site's points in the working copy as the last sit_grouped_recenter_step left it (the hulls
+ * SiteVolumes.py:63-69 asks qhull for), one workgroup per site, the copy is only read: volumes[K], status[K],
+ * n_facets[K] (triangles found, also where the site did not close) and, optional, vertex_mask[N]: 1 for the grouped
+ * elements that are vertices of their site's hull (of equal points the first).  Gift wrapping with a certified
+ * orientation test (csrc/hull_predicates.h: double arithmetic with a forward error bound, never a decision from a
+ * determinant inside its bound).  status 0: the hull closed (every directed edge met its reverse once, V - E + F = 2)
+ * and volumes[s] is its volume - the tetrahedra against the first vertex summed in the order the facets were found, the
+ * same bytes in every run; 1: fewer than 4 points; 2: an uncertain test was met (coplanar or nearly coplanar points);
+ * 3: more than the facet or open-edge capacity of sit_hull_plan; 4: the hull did not close.  volumes[s] is NaN unless
+ * status[s] is 0: the caller takes such a site elsewhere (sit_grouped_work_fetch).  SIT_ERR_INVALID before step 0 of a
+ * recentring, and for a stale grouping as the other sit_grouped_* calls.                                              */
+int sit_grouped_hull_volumes(sit_ctx *ctx, double *volumes, int32_t *status, int32_t *n_facets, uint8_t *vertex_mask);
+/* Elements [first, first + n) of the working copy: pts [n, 3].  SIT_ERR_INVALID before step 0 of a recentring.       */
+int sit_grouped_work_fetch(sit_ctx *ctx, int64_t first, int64_t n, double *pts);
+/* The plan of sit_grouped_hull_volumes, no context needed: out4 = {facet capacity, open-edge capacity, threads per
+ * workgroup, LDS bytes per workgroup} (csrc/hull_plan.h).                                                            */
+int sit_hull_plan(int64_t *out4);
 
 /* ---- the site graph under periodic boundaries (network/DiffusionPathwayAnalysis.py) ------------------------------------ */
 

@@ -40,7 +40,7 @@ class FillParams(C.Structure):
                    int(store_rows), int(assign), int(predict_normed), int(defer), float(predict_threshold))
 
 
-ABI_VERSION = 8          # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
+ABI_VERSION = 9          # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
 
 
 # every symbol include/sitator_hip.h declares: (restype, argtypes)
@@ -109,6 +109,9 @@ SIGNATURES = {
     "sit_grouped_recenter_step": (C.c_int, [_vp, i64, i64, _dp]),
     "sit_group_plan": (C.c_int, [i64, i64, _ip]),
     "sit_group_info": (C.c_int, [_vp, _dp, C.c_int]),
+    "sit_grouped_hull_volumes": (C.c_int, [_vp, _dp, _i32p, _i32p, _u8p]),
+    "sit_grouped_work_fetch": (C.c_int, [_vp, i64, i64, _dp]),
+    "sit_hull_plan": (C.c_int, [_ip]),
     "sit_pathway_components": (C.c_int, [_vp, i64, _u8p, _dp, C.c_int, _i32p, _i32p, _ip]),
     "sit_comm_unique_id": (C.c_int, [_u8p]),
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
@@ -173,6 +176,14 @@ def group_plan(n_entries, K):
     if load().sit_group_plan(int(n_entries), int(K), _i(out)) != OK:
         raise ValueError("group_plan: beyond the capacity of group_by_site")
     return int(out[0]), int(out[1]), bool(out[2]), int(out[3])
+
+
+def hull_plan():
+    """``(facet capacity, open-edge capacity, threads per workgroup, LDS bytes per workgroup)`` of ``grouped_hull_volumes``
+    (``sit_hull_plan``)."""
+    out = np.zeros(4, dtype=np.int64)
+    load().sit_hull_plan(_i(out))
+    return tuple(int(v) for v in out)
 
 
 def release_cached_memory():
@@ -845,11 +856,36 @@ class HipContext(object):
         self._check_index(self.lib.sit_grouped_recenter_step(self._h, int(i), int(n_recenterings), None if out is None else _d(out)))
         return out
 
+    def grouped_hull_volumes(self, K, vertex_mask=False):
+        """``(volumes [K], status int32 [K], n_facets int32 [K], vertex_mask uint8 [N] or None)``: the convex hull of every
+        site's points in the working copy as the last ``grouped_recenter_step`` left it (``sit_grouped_hull_volumes``).
+        ``status`` 0: closed, the volume is the hull's; 1: fewer than 4 points; 2: an uncertain orientation test; 3: beyond
+        the capacity of ``hull_plan()``; 4: not closed - the volume is NaN for all of these.  ``ValueError`` before step 0
+        and for a stale grouping."""
+        info = self.group_info()
+        if int(K) != info["n_sites"]:
+            raise ValueError("grouped_hull_volumes: K is not the number of sites of the grouping")
+        vols = np.empty(int(K))
+        status = np.empty(int(K), dtype=np.int32)
+        nf = np.empty(int(K), dtype=np.int32)
+        mask = np.zeros(info["n_grouped"], dtype=np.uint8) if vertex_mask else None
+        self._check(self.lib.sit_grouped_hull_volumes(self._h, _d(vols), status.ctypes.data_as(_i32p), nf.ctypes.data_as(_i32p),
+                                                      None if mask is None else mask.ctypes.data_as(_u8p)))
+        return vols, status, nf, mask
+
+    def grouped_work_fetch(self, first, n):
+        """``points [n, 3]`` of the elements ``[first, first + n)`` of the recentred working copy
+        (``sit_grouped_work_fetch``)."""
+        n = int(n)
+        pts = np.empty((n, 3))
+        self._check(self.lib.sit_grouped_work_fetch(self._h, int(first), n, _d(pts)))
+        return pts
+
     def group_info(self):
-        v = np.zeros(7)
-        self.lib.sit_group_info(self._h, _d(v), 7)
+        v = np.zeros(8)
+        self.lib.sit_group_info(self._h, _d(v), 8)
         return {"n_grouped": int(v[0]), "n_sites": int(v[1]), "chunks": int(v[2]), "lds": bool(v[3]), "group_ms": float(v[4]),
-                "bucket_avg_ms": float(v[5]), "recenter_ms": float(v[6])}
+                "bucket_avg_ms": float(v[5]), "recenter_ms": float(v[6]), "hull_ms": float(v[7])}
 
     # -- DiffusionPathwayAnalysis: reads nothing of the context but its cell
     def pathway_components(self, conn, centers, n_images=27, codes=False):
@@ -993,6 +1029,6 @@ for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "a
               "site_anchors", "site_sums", "check_occupancy", "site_counts", "cooccupancy", "jump_sources", "jump_list",
               "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
               "unknown_runs", "replace_closer", "clamp_trajectory", "group_by_site", "grouped_fetch", "grouped_bucket_averages",
-              "grouped_recenter_step", "min_image", "pathway_components"):
+              "grouped_recenter_step", "grouped_hull_volumes", "grouped_work_fetch", "min_image", "pathway_components"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

@@ -2,7 +2,7 @@
 // sites at once: a stable counting sort of the assigned entries e = frame * M + ion by their label (group_plan.h has the
 // plan), and on the grouped points the arithmetic of the two consumers that loop over the sites in the reference:
 // misc/NAvgsPerSite.py (bucket averages with PBCCalculator.average) and site_descriptors/SiteVolumes.py:51-77 (cumulative
-// recentring; the hulls stay on the host).
+// recentring; the hulls of the recentred copy are hull.hip's).
 //
 // Order.  Sites ascending, inside a site ascending e: the order of real_traj[:, mobile_mask][traj == site].  A chunk of
 // entries belongs to one wave that walks it tile by tile in ascending e, so the rank of an entry among the equal labels
@@ -32,7 +32,7 @@ struct GroupState {
     int lds = 1;
     i64 recenter_next = 0, recenter_n = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double ms_group = 0, ms_avg = 0, ms_recenter = 0;
+    double ms_group = 0, ms_avg = 0, ms_recenter = 0, ms_hull = 0;
 };
 
 GroupState *state_of(sit_ctx *c)
@@ -483,12 +483,27 @@ extern "C" int sit_grouped_recenter_step(sit_ctx *c, i64 i, i64 n_recenterings, 
     return SIT_OK;
 }
 
+// hull.hip: the working copy once step 0 has been taken
+int group_working_copy(sit_ctx *c, const char *who, GroupWork *out)
+{
+    GroupState *g = nullptr;
+    int rc = current_grouping(c, who, &g);
+    if (rc) return rc;
+    if (g->recenter_next < 1 || (g->N > 0 && !g->work)) {
+        c->msg = std::string(who) + ": no working copy (sit_grouped_recenter_step from step 0 first)";
+        return SIT_ERR_INVALID;
+    }
+    out->work = g->work; out->d_offsets = g->d_offsets; out->N = g->N; out->K = g->K;
+    out->ev0 = g->ev0; out->ev1 = g->ev1; out->ms_hull = &g->ms_hull;
+    return SIT_OK;
+}
+
 extern "C" int sit_group_info(sit_ctx *c, double *out, int n)
 {
     if (!c || !out) return SIT_ERR_INVALID;
     const GroupState *g = (const GroupState *)c->group;
-    const double v[7] = {g ? (double)g->N : 0.0, g ? (double)g->K : 0.0, g ? (double)g->n_chunks : 0.0, g ? (double)g->lds : 0.0,
-                         g ? g->ms_group : 0.0, g ? g->ms_avg : 0.0, g ? g->ms_recenter : 0.0};
-    for (int k = 0; k < n; k++) out[k] = k < 7 ? v[k] : 0.0;
+    const double v[8] = {g ? (double)g->N : 0.0, g ? (double)g->K : 0.0, g ? (double)g->n_chunks : 0.0, g ? (double)g->lds : 0.0,
+                         g ? g->ms_group : 0.0, g ? g->ms_avg : 0.0, g ? g->ms_recenter : 0.0, g ? g->ms_hull : 0.0};
+    for (int k = 0; k < n; k++) out[k] = k < 8 ? v[k] : 0.0;
     return SIT_OK;
 }

@@ -497,6 +497,15 @@ int sit_label_counts(sit_ctx *c, bool zero = true);              // zero = false
 void fitfast_free(sit_ctx *c);
 void spectrum_free(sit_ctx *c);
 void group_free(sit_ctx *c);
+// group.hip: the recentred working copy of the current grouping for hull.hip (SIT_ERR_INVALID: none, stale, or no step taken)
+struct GroupWork {
+    const double *work;               // [N, 3]
+    const i64 *d_offsets;             // [K + 1], device
+    i64 N, K;
+    hipEvent_t ev0, ev1;
+    double *ms_hull;                  // sit_group_info [7]
+};
+int group_working_copy(sit_ctx *c, const char *who, GroupWork *out);
 bool fitfast_valid(sit_ctx *c);
 void fitfast_invalidate(sit_ctx *c);
 int fitfast_set_state(sit_ctx *c, const double *cen, const i64 *cnt, i64 K);

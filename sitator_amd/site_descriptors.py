@@ -1,6 +1,8 @@
 """``SiteVolumes`` (reference: ``sitator/site_descriptors/SiteVolumes.py``): the recentring of every site's point cloud runs on
-the GPU for all sites at once (``sit_grouped_recenter_step``), the convex hulls stay on the host (qhull)."""
+the GPU for all sites at once (``sit_grouped_recenter_step``); the convex hulls are qhull's on the host (``hulls="host"``, the
+default) or the device's (``hulls="device"``: ``sit_grouped_hull_volumes``, with qhull for the sites it flags)."""
 import logging
+import time
 
 import numpy as np
 
@@ -28,10 +30,27 @@ class SiteVolumes(object):
     """Volumes of sites.
 
     ``error_on_insufficient_coord``: ``compute_volumes`` needs at least 4 vertices per site; a site with fewer raises
-    ``InsufficientCoordinatingAtomsError`` (``True``) or gets volume 0 and surface area NaN (``False``)."""
+    ``InsufficientCoordinatingAtomsError`` (``True``) or gets volume 0 and surface area NaN (``False``).
 
-    def __init__(self, error_on_insufficient_coord=True):
+    ``hulls``: where ``compute_accessable_volumes`` takes its convex hulls.  ``"host"``: every recentred cloud comes back and
+    goes through ``scipy.spatial.ConvexHull``, as in the reference.  ``"device"``: the clouds stay on the GPU and are wrapped
+    there with a certified orientation test; a site the device does not close with certified signs (coplanar points, fewer
+    than 4, more facets than its capacity) is fetched on its own and goes through the host branch, warning and ``inf`` rule
+    included.  The device's volume of a closed hull differs from qhull's in the last digits.  After a
+    call ``last_hull_status`` maps every device status (0 closed, 1 few points, 2 uncertain sign, 3 capacity, 4 not closed)
+    to the number of hulls (sites x recentrings) that ended with it, and ``last_hull_times`` holds the seconds spent in the
+    recentring kernels, the hull kernels, the fetches of flagged sites and their host hulls, and the largest facet count.
+    ``compute_volumes`` always runs on the host."""
+
+    HULLS = ("host", "device")
+
+    def __init__(self, error_on_insufficient_coord=True, hulls="host"):
+        if hulls not in self.HULLS:
+            raise ValueError("hulls must be one of %r, not %r" % (self.HULLS, hulls))
         self.error_on_insufficient_coord = error_on_insufficient_coord
+        self.hulls = hulls
+        self.last_hull_status = None
+        self.last_hull_times = None
 
     def compute_accessable_volumes(self, st, n_recenterings=8):
         """The volume of the convex hull around all positions assigned to a site: the minimum over ``n_recenterings``
@@ -41,7 +60,8 @@ class SiteVolumes(object):
         The points are grouped by site on the GPU; every recentring step shifts and wraps all sites' points there, in
         place and cumulatively as the reference does, and comes back as one array - bit-equal to the reference's, so the
         hulls (``scipy.spatial.ConvexHull``, on the host) are the reference's.  A hull qhull refuses is logged and skipped;
-        if all of a site's are refused its volume is ``inf``.  A site without points raises ``IndexError``."""
+        if all of a site's are refused its volume is ``inf``.  A site without points raises ``IndexError``.  With
+        ``hulls="device"`` nothing comes back but the volumes and the flagged sites (see the class)."""
         assert isinstance(st, SiteTrajectory)
         return self._accessible(st, st.group_real_positions(), n_recenterings)
 
@@ -52,6 +72,8 @@ class SiteVolumes(object):
         return self._accessible(st, st.group_real_positions(_resident=True), n_recenterings)
 
     def _accessible(self, st, grouping, n_recenterings):
+        if self.hulls == "device":
+            return self._accessible_device(st, grouping, n_recenterings)
         ConvexHull, QhullError = _hull_tools()
         K = grouping.n_sites
         offsets = grouping.offsets
@@ -67,6 +89,46 @@ class SiteVolumes(object):
                     continue
                 if hull.volume < vols[site]:
                     vols[site] = hull.volume
+        st.site_network.add_site_attribute("accessable_site_volumes", vols)
+        return vols
+
+    def _accessible_device(self, st, grouping, n_recenterings):
+        ConvexHull, QhullError = _hull_tools()
+        ctx = grouping._ctx
+        K = grouping.n_sites
+        offsets = grouping.offsets
+        vols = np.full(K, np.inf)
+        counts = dict((k, 0) for k in range(5))
+        times = {"recenter": 0.0, "hull": 0.0, "fetch": 0.0, "fallback": 0.0, "max_facets": 0}
+        for i in range(int(n_recenterings)):
+            ctx.grouped_recenter_step(i, n_recenterings, None)
+            v, status, n_facets, _ = ctx.grouped_hull_volumes(K)
+            info = ctx.group_info()
+            times["recenter"] += 1e-3 * info["recenter_ms"]
+            times["hull"] += 1e-3 * info["hull_ms"]
+            if K:
+                times["max_facets"] = max(times["max_facets"], int(n_facets.max()))
+            for k, n in zip(*np.unique(status, return_counts=True)):
+                counts[int(k)] = counts.get(int(k), 0) + int(n)
+            closed = status == 0
+            better = closed & (v < vols)
+            vols[better] = v[better]
+            for site in np.nonzero(~closed)[0]:
+                t0 = time.perf_counter()
+                pts = ctx.grouped_work_fetch(int(offsets[site]), int(offsets[site + 1] - offsets[site]))
+                t1 = time.perf_counter()
+                try:
+                    hull = ConvexHull(pts)
+                except QhullError as qhe:
+                    logger.warning("For site %i, iter %i: %s" % (site, i, qhe))
+                    hull = None
+                if hull is not None and hull.volume < vols[site]:
+                    vols[site] = hull.volume
+                times["fetch"] += t1 - t0
+                times["fallback"] += time.perf_counter() - t1
+        self.last_hull_status = counts
+        self.last_hull_times = times
+        logger.info("device hulls by status: %r; %d of %d went to the host" % (counts, sum(counts.values()) - counts[0], sum(counts.values())))
         st.site_network.add_site_attribute("accessable_site_volumes", vols)
         return vols
 
