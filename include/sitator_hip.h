@@ -70,7 +70,7 @@ const char *sit_last_message(sit_ctx *ctx);
  * frame), out[5] = bytes of a communicator id (sit_comm_unique_id).  Writes min(n, 6) words and returns 6.  A binding
  * checks its own struct declarations against these once, at import (tests/test_abi.py does it for the ctypes stubs of
  * INTEGRATION.md and sitator_amd/_lib.py).  No context, no GPU needed.                                        */
-#define SIT_ABI_VERSION 9
+#define SIT_ABI_VERSION 10
 int sit_abi(int32_t *out, int n);
 /* Device buffers of 1 MB and more (the trajectory, the landmark rows, labels, the fit's arena) are kept by the process
  * when a context lets go of them, up to as much as its contexts have held at once, and handed to the next context that asks for a similar size: a process
@@ -448,6 +448,32 @@ int sit_hull_plan(int64_t *out4);
  * cell: frames, rows, labels and their validity stay as they are.                                          */
 int sit_pathway_components(sit_ctx *ctx, int64_t K, const uint8_t *conn, const double *centers, int n_images,
                            int32_t *code, int32_t *root, int64_t *rounds);
+
+/* ---- energy barriers between sites (network/MergeSitesByBarrier.py) ---------------------------------------------------------- */
+
+/* The energies of ONE mobile atom driven along the straight path of every candidate pair, in the frozen lattice static_pos[S, 3]
+ * under the context's cell, and the verdict of :116-125 on them.  The potential is a truncated and shifted 12-6 pair term of
+ * the mobile atom with every coordinating atom s and all its periodic images (csrc/barrier_plan.h): with d2 the squared
+ * distance, s6 = (sigma[s]^2 / d2)^3, phi = 4 eps[s] s6 (s6 - 1) - e0[s] for d2 <= rc^2, e0[s] the same expression at
+ * d2 = rc^2; d2 = 0 gives +inf.  Everything else of the total energy the reference's calculator returns (:113) is constant
+ * along a path and is left out.  pairs[P, 2] (int32) names sites of centers[K, 3]; per pair (i, j) the point pos[j] is moved to
+ * its image nearest pos[i] as sit_min_image does (code[P], optional: its 100 i + 10 j + k), vector = moved - pos[i], and image m
+ * of n sits at vector * coeffs[m] + pos[i] (the product rounded before the sum, :110-112; the caller passes
+ * np.linspace(0, 1, n)).  energies[P, n] (optional).  verdict[P, 3] (uint8): [0] the first maximum of the pair's energies (np.argmax)
+ * is neither its first nor its last image, [1] maximum - first <= threshold, [2] maximum - last <= threshold.  Complete for any
+ * cell shape, cells shorter than rc, and atoms or driven points outside the cell; the sum runs in a fixed order (no atomics):
+ * the same bytes on every call.  SIT_ERR_INVALID: a missing array, S < 1, n < 3, K > 16384, a pair index outside [0, K), a
+ * non-positive (or not finite) eps, sigma or rc, rc beyond 255 perpendicular heights of the cell, a position that is not finite
+ * or more than 2^20 cells from the origin, a coefficient outside [-2, 2].  P = 0 is SIT_OK and touches nothing.  Reads nothing
+ * of the context but its cell: frames, rows, labels and their validity stay as they are.                                  */
+int sit_barrier_energies(sit_ctx *ctx, const double *static_pos, const double *eps, const double *sigma, int64_t S, double rc,
+                         const double *centers, int64_t K, const int32_t *pairs, int64_t P, const double *coeffs, int64_t n,
+                         double threshold, double *energies, uint8_t *verdict, int32_t *code);
+/* The plan of sit_barrier_energies for cell[9] (rows are the cell vectors) and rc, no context needed: out6 = {the translations
+ * |t_a| <= out6[a] along the three cell vectors that can hold a term within rc once the difference of two points is brought
+ * into the cell (floor(rc / h_a) + 1, h_a the perpendicular height), static atoms per LDS tile, threads per workgroup, LDS
+ * bytes per workgroup}.  SIT_ERR_INVALID: a degenerate cell, rc not positive or beyond 255 heights.                        */
+int sit_barrier_plan(const double *cell, double rc, int64_t *out6);
 
 /* ---- frame sharding across GPUs ------------------------------------ */
 

@@ -18,7 +18,8 @@ from .dynamics import (AverageVibrationalFrequency, GenerateClampedTrajectory, J
 from .merging import MergeSites, MergeSitesError, MergedSitesTooDistantError  # noqa: F401
 from .recenter import RecenterTrajectory  # noqa: F401
 from .misc import NAvgsPerSite  # noqa: F401
-from .network import DiffusionPathwayAnalysis  # noqa: F401
+from .network import DiffusionPathwayAnalysis, MergeSitesByBarrier  # noqa: F401
+from . import calculators  # noqa: F401
 from .site_descriptors import InsufficientCoordinatingAtomsError, SiteVolumes  # noqa: F401
 
 __version__ = "0.1.0"

@@ -40,7 +40,7 @@ class FillParams(C.Structure):
                    int(store_rows), int(assign), int(predict_normed), int(defer), float(predict_threshold))
 
 
-ABI_VERSION = 9          # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
+ABI_VERSION = 10         # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
 
 
 # every symbol include/sitator_hip.h declares: (restype, argtypes)
@@ -113,6 +113,9 @@ SIGNATURES = {
     "sit_grouped_work_fetch": (C.c_int, [_vp, i64, i64, _dp]),
     "sit_hull_plan": (C.c_int, [_ip]),
     "sit_pathway_components": (C.c_int, [_vp, i64, _u8p, _dp, C.c_int, _i32p, _i32p, _ip]),
+    "sit_barrier_energies": (C.c_int, [_vp, _dp, _dp, _dp, i64, C.c_double, _dp, i64, _i32p, i64, _dp, i64, C.c_double, _dp, _u8p,
+                                       _i32p]),
+    "sit_barrier_plan": (C.c_int, [_dp, C.c_double, _ip]),
     "sit_comm_unique_id": (C.c_int, [_u8p]),
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
     "sit_comm_destroy": (C.c_int, [_vp]),
@@ -184,6 +187,16 @@ def hull_plan():
     out = np.zeros(4, dtype=np.int64)
     load().sit_hull_plan(_i(out))
     return tuple(int(v) for v in out)
+
+
+def barrier_plan(cell, rc):
+    """``{"translations": (n0, n1, n2), "tile": static atoms per LDS tile, "threads": per workgroup, "lds_bytes": per workgroup}``
+    of ``barrier_energies`` for ``cell`` (rows are the cell vectors) and the cutoff ``rc`` (``sit_barrier_plan``)."""
+    out = np.zeros(6, dtype=np.int64)
+    cell = _f64(cell).reshape(3, 3)
+    if load().sit_barrier_plan(_d(cell), float(rc), _i(out)) != OK:
+        raise ValueError("barrier_plan: a degenerate cell, or rc not positive or beyond 255 perpendicular heights of the cell")
+    return {"translations": tuple(int(v) for v in out[:3]), "tile": int(out[3]), "threads": int(out[4]), "lds_bytes": int(out[5])}
 
 
 def release_cached_memory():
@@ -906,6 +919,30 @@ class HipContext(object):
                                                     root.ctypes.data_as(_i32p), C.byref(rounds)))
         return root, int(rounds.value), code
 
+    # -- MergeSitesByBarrier: reads nothing of the context but its cell
+    def barrier_energies(self, static_pos, eps, sigma, rc, centers, pairs, coeffs, threshold, energies=True, codes=False):
+        """``(energies [P, n] or None, verdict uint8 [P, 3], code int32 [P] or None)`` (``sit_barrier_energies``): per pair
+        ``(i, j)`` of ``pairs`` ``[P, 2]`` the energy of one mobile atom at the ``n`` points ``vector * coeffs[m] + centers[i]``
+        (``vector``: from ``centers[i]`` to the nearest image of ``centers[j]``) among the atoms ``static_pos`` ``[S, 3]`` and
+        all their periodic images, under the truncated and shifted 12-6 potential of ``eps`` / ``sigma`` ``[S]`` and ``rc``;
+        ``verdict``: the maximum is interior, forward barrier <= ``threshold``, backward barrier <= ``threshold``; ``code``:
+        the ``min_image`` code of the pair.  Anything that does not fit raises ``ValueError``."""
+        static_pos = _f64(static_pos).reshape(-1, 3)
+        eps, sigma = _f64(eps).reshape(-1), _f64(sigma).reshape(-1)
+        assert len(eps) == len(static_pos) == len(sigma)
+        centers = _f64(centers).reshape(-1, 3)
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        coeffs = _f64(coeffs).reshape(-1)
+        P, n = len(pairs), len(coeffs)
+        en = np.empty((P, n)) if energies else None
+        verdict = np.zeros((P, 3), dtype=np.uint8)
+        code = np.zeros(P, dtype=np.int32) if codes else None
+        self._check(self.lib.sit_barrier_energies(
+            self._h, _d(static_pos), _d(eps), _d(sigma), len(static_pos), float(rc), _d(centers), len(centers),
+            pairs.ctypes.data_as(_i32p), P, _d(coeffs), n, float(threshold), None if en is None else _d(en),
+            verdict.ctypes.data_as(_u8p), None if code is None else code.ctypes.data_as(_i32p)))
+        return en, verdict, code
+
     # ---- RCCL exchange of the frame-sharded path (csrc/comm.hip) ----
     def comm_create(self, unique_id, rank, world):
         uid = np.frombuffer(bytes(unique_id), dtype=np.uint8).copy()
@@ -1029,6 +1066,7 @@ for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "a
               "site_anchors", "site_sums", "check_occupancy", "site_counts", "cooccupancy", "jump_sources", "jump_list",
               "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
               "unknown_runs", "replace_closer", "clamp_trajectory", "group_by_site", "grouped_fetch", "grouped_bucket_averages",
-              "grouped_recenter_step", "grouped_hull_volumes", "grouped_work_fetch", "min_image", "pathway_components"):
+              "grouped_recenter_step", "grouped_hull_volumes", "grouped_work_fetch", "min_image", "pathway_components",
+              "barrier_energies"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

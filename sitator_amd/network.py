@@ -1,5 +1,6 @@
 """``sitator.network`` on the device: ``DiffusionPathwayAnalysis`` (``network/DiffusionPathwayAnalysis.py``), the step after
-``JumpAnalysis`` that says which sites form pathways crossing the periodic cell.
+``JumpAnalysis`` that says which sites form pathways crossing the periodic cell, and ``MergeSitesByBarrier``
+(``network/MergeSitesByBarrier.py``), which merges sites that a low energy barrier separates (at the end of this file).
 
 The reference builds the graph of the 3 x 3 x 3 supercell with one Python call per edge per image and hands it to scipy.  Here
 the image code of every connected pair, the edge list and the connected components of the 27 K nodes come from
@@ -13,6 +14,9 @@ import numbers
 import numpy as np
 
 from . import _lib
+from .calculators import LennardJones
+from .merging import MergeSites
+from .pbc import PBCCalculator
 
 logger = logging.getLogger(__name__)
 
@@ -166,3 +170,84 @@ class DiffusionPathwayAnalysis(object):
         if return_direction:
             out.append(directions)
         return tuple(out)
+
+
+class MergeSitesByBarrier(MergeSites):
+    """Merge sites based on the energy barrier between them (``sitator.network.MergeSitesByBarrier``).
+
+    For every pair of sites within ``maximum_pairwise_distance`` that exchanged at least ``minimum_jumps_mergable`` jumps, one
+    mobile atom is driven in ``n_driven_images`` evenly spaced steps along the straight line from one centre to the nearest
+    image of the other, in the frozen lattice of the atoms of ``coordinating_mask`` (default: the static atoms).  If the highest
+    image is neither end of the path, the pair is mergable from i to j when that image lies at most ``barrier_threshold`` above
+    the first one, and from j to i when it lies at most ``barrier_threshold`` above the last one; if it is an end, the two sites
+    share a basin and the pair stays as the distance and the jump counts left it.  The strongly connected components of the
+    mergable matrix are merged (further keywords go to ``MergeSites``).
+
+    :param calculator: a ``sitator_amd.calculators.LennardJones``.
+    :param float barrier_threshold: the barrier above which two sites are not mergable (units of ``epsilon``).
+    :param int n_driven_images: at least 3.
+    :param float maximum_pairwise_distance, maximum_merge_distance: Angstrom.
+    :param int minimum_jumps_mergable: compared with ``n_ij``.
+
+    All image energies of all pairs come from one call of ``sit_barrier_energies`` (``csrc/barrier.hip``); they hold the mobile
+    atom's energy only - the energy of the lattice with itself, which the reference's calculator includes in every total, is
+    the same for all images and drops out of both barriers.  After ``run()`` the operator keeps ``pairs_`` ``[P, 2]`` (i < j, in
+    the reference's order), ``energies_`` ``[P, n_driven_images]`` and ``mergable_`` ``[K, K]``, the matrix handed to
+    ``connected_components``.
+
+    Deliberate departures from the reference:
+
+    * ``calculator`` is not an arbitrary ASE calculator: anything but a ``LennardJones`` raises ``TypeError``.  The energies
+      are evaluated on the device and there is no CPU fallback.
+    * Without ``n_ij`` on the network a ``JumpAnalysis`` is run first.  The reference means to (:72-74) but never imports
+      ``JumpAnalysis`` and ends in ``NameError``.
+    """
+
+    def __init__(self, calculator, barrier_threshold, n_driven_images=20, maximum_pairwise_distance=2, minimum_jumps_mergable=1,
+                 maximum_merge_distance=2, **kwargs):
+        super(MergeSitesByBarrier, self).__init__(maximum_merge_distance=maximum_merge_distance, **kwargs)
+        if not isinstance(calculator, LennardJones):
+            raise TypeError("MergeSitesByBarrier: `calculator` must be a sitator_amd.calculators.LennardJones, not %s: the "
+                            "energies are evaluated on the device and there is no CPU fallback" % type(calculator).__name__)
+        self.barrier_threshold = barrier_threshold
+        self.maximum_pairwise_distance = maximum_pairwise_distance
+        self.minimum_jumps_mergable = minimum_jumps_mergable
+        assert n_driven_images >= 3, "Must have at least initial, transition, and final."
+        self.n_driven_images = n_driven_images
+        self.calculator = calculator
+        self.pairs_ = self.energies_ = self.mergable_ = None
+
+    def _get_sites_to_merge(self, st, coordinating_mask=None):
+        from scipy.sparse.csgraph import connected_components
+        sn = st.site_network
+        if not sn.has_attribute('n_ij'):                         # :72-74
+            from .dynamics import JumpAnalysis
+            JumpAnalysis().run(st)
+        pos = np.asarray(sn.centers, dtype=np.float64)
+        if coordinating_mask is None:                            # :77-80
+            coordinating_mask = sn.static_mask
+        else:
+            coordinating_mask = np.asarray(coordinating_mask, dtype=bool)
+            assert not np.any(coordinating_mask & sn.mobile_mask)
+        static_pos = np.asarray(sn.structure.get_positions(), dtype=np.float64)[coordinating_mask]
+        eps, sigma = self.calculator.parameters_for(np.asarray(sn.structure.get_atomic_numbers())[coordinating_mask])
+        interpolation_coeffs = np.linspace(0, 1, self.n_driven_images)   # :87
+
+        # -- Decide on pairs to check (:90-101)
+        pbcc = PBCCalculator(np.asarray(sn.structure.cell, dtype=np.float64))
+        dists = pbcc.pairwise_distances(pos)
+        mergable = dists <= self.maximum_pairwise_distance
+        mergable &= np.asarray(sn.n_ij) >= self.minimum_jumps_mergable
+        first, second = np.nonzero(np.triu(mergable | mergable.T, k=1))   # the order of itertools.combinations
+        pairs = np.stack([first, second], axis=1).astype(np.int32)
+
+        # -- Check pairs' barriers (:103-125)
+        energies, verdict, _ = pbcc._ctx.barrier_energies(static_pos, eps, sigma, self.calculator.rc, pos, pairs,
+                                                          interpolation_coeffs, self.barrier_threshold)
+        interior = verdict[:, 0] != 0
+        mergable[first[interior], second[interior]] = verdict[interior, 1] != 0
+        mergable[second[interior], first[interior]] = verdict[interior, 2] != 0
+        self.pairs_, self.energies_, self.mergable_ = pairs, energies, mergable.copy()
+
+        n_merged_sites, labels = connected_components(mergable, directed=True, connection='strong')   # :128-132
+        return [np.where(labels == lbl)[0] for lbl in range(n_merged_sites)]
