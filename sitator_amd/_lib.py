@@ -604,10 +604,8 @@ class HipContext(object):
         K = int(K)
         co = np.zeros((K, K), dtype=np.uint8)
         rc = self.lib.sit_cooccupancy(self._h, K, co.ctypes.data_as(_u8p))
-        if rc == E_INVALID and self.message().startswith("index "):
-            # a label beyond the sites: the reference's connmat[site, frame] raises this (MergeSitesByThreshold.py:70)
-            raise IndexError(self.message())
-        self._check(rc)
+        # a label beyond the sites: the reference's connmat[site, frame] raises this (MergeSitesByThreshold.py:70)
+        self._check_index(rc)
         return co.view(np.bool_)
 
     JUMP_NONE = -(1 << 63)
@@ -647,10 +645,8 @@ class HipContext(object):
         rc = self.lib.sit_jump_analysis(self._h, int(K), None if lin is None else _i(lin),
                                         None if tin is None else _i(tin), _d(n_ij), _d(tsum), _i(tn), _i(total),
                                         C.byref(nprob), _i(lout), _i(tout))
-        if rc == E_INVALID and self.message().startswith("index "):
-            # a label beyond the site tables: the reference's fancy indexing raises this (dynamics/JumpAnalysis.py:75-88)
-            raise IndexError(self.message())
-        self._check(rc)
+        # a label beyond the site tables: the reference's fancy indexing raises this (dynamics/JumpAnalysis.py:75-88)
+        self._check_index(rc)
         return n_ij, tsum, tn, total, nprob.value, lout, tout
 
     def assign_last_known(self, frame_threshold, last_known_in=None, time_unknown_in=None, out=None):
@@ -722,10 +718,8 @@ class HipContext(object):
         out = np.empty((self.F, self.M), dtype=np.int64)
         rc = self.lib.sit_replace_closer(self._h, _i(records), len(records), _d(centers), len(centers), _d(positions),
                                          len(positions), _i(out))
-        if rc == E_INVALID and self.message().startswith("index "):
-            # a label beyond the sites: the reference's centers[before_site] raises this (ReplaceUnassignedPositions.py:75)
-            raise IndexError(self.message())
-        self._check(rc)
+        # a label beyond the sites: the reference's centers[before_site] raises this (ReplaceUnassignedPositions.py:75)
+        self._check_index(rc)
         return out
 
     def running_mode(self, wleft, wright, threshold, replace_unknown, n_sites=0):
@@ -808,10 +802,8 @@ class HipContext(object):
             C.byref(first))
         if rc == E_UNASSIGNED:
             raise errors.UnassignedClampError(first.value)
-        if rc == E_INVALID and self.message().startswith("index "):
-            # a label beyond the sites: the reference's centers_c[at_site] reads past the table (GenerateClampedTrajectory.pyx:99)
-            raise IndexError(self.message())
-        self._check(rc)
+        # a label beyond the sites: the reference's centers_c[at_site] reads past the table (GenerateClampedTrajectory.pyx:99)
+        self._check_index(rc)
         return out
 
     # -- per-site point clouds: reads labels and frames only (labels_version, rows and labels stay)

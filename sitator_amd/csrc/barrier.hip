@@ -13,12 +13,6 @@
 #include "pathway_graph.h"
 #include "barrier_plan.h"
 
-namespace {
-struct BrImages { double img[27][3]; };                          // by value: kernel arguments, read with scalar loads
-
-inline i64 up64(i64 bytes) { return (bytes + 63) & ~(i64)63; }
-}
-
 // the staged form of the static atoms (bp_atom): rec[s * BP_REC ...]
 __global__ __launch_bounds__(BP_BLOCK) void k_barrier_atoms(Pbc pbc, const double *pos, const double *eps, const double *sigma, double rc, i64 S,
                                                             double *rec)
@@ -31,7 +25,7 @@ __global__ __launch_bounds__(BP_BLOCK) void k_barrier_atoms(Pbc pbc, const doubl
     for (int k = 0; k < BP_REC; k++) rec[s * BP_REC + k] = r[k];
 }
 
-__global__ __launch_bounds__(BP_BLOCK) void k_barrier_energies(Pbc pbc, BarrierPlan pl, BrImages I, const double *rec, i64 S, const double *centers,
+__global__ __launch_bounds__(BP_BLOCK) void k_barrier_energies(Pbc pbc, BarrierPlan pl, Images27 I, const double *rec, i64 S, const double *centers,
                                                                const i32 *pairs, const double *coeffs, int n, double threshold,
                                                                double *energies, unsigned char *verdict, i32 *code)
 {
@@ -121,25 +115,25 @@ extern "C" int sit_barrier_energies(sit_ctx *c, const double *static_pos, const 
     for (i64 k = 0; k < n; k++) SIT_REQUIRE(c, fabs(coeffs[k]) <= 2.0, "sit_barrier_energies: an interpolation coefficient outside [-2, 2]");
     HIP_TRY(c, hipSetDevice(c->device));
 
-    // scratch: records | raw positions | eps | sigma | centres | pairs | coefficients | energies | verdicts | codes
-    const i64 o_rec = 0, o_pos = o_rec + up64(S * BP_REC * 8), o_eps = o_pos + up64(S * 24), o_sig = o_eps + up64(S * 8);
-    const i64 o_cen = o_sig + up64(S * 8), o_pair = o_cen + up64(K * 24), o_coef = o_pair + up64(P * 8), o_en = o_coef + up64(n * 8);
-    const i64 o_ver = o_en + up64(P * n * 8), o_code = o_ver + up64(P * 3), total = o_code + up64(P * 4);
-    int rc_;
-    if ((rc_ = ensure_scratch(c, total))) return rc_;
-    char *base = (char *)c->d_scratch;
-    double *d_rec = (double *)(base + o_rec), *d_pos = (double *)(base + o_pos), *d_eps = (double *)(base + o_eps);
-    double *d_sig = (double *)(base + o_sig), *d_cen = (double *)(base + o_cen), *d_coef = (double *)(base + o_coef);
-    double *d_en = (double *)(base + o_en);
-    i32 *d_pair = (i32 *)(base + o_pair), *d_code = (i32 *)(base + o_code);
-    unsigned char *d_ver = (unsigned char *)(base + o_ver);
+    // scratch, every piece on a 64-byte boundary: records | raw positions | eps | sigma | centres | pairs | coefficients |
+    // energies | verdicts | codes
+    double *d_rec, *d_pos, *d_eps, *d_sig, *d_cen, *d_coef, *d_en;
+    i32 *d_pair, *d_code;
+    unsigned char *d_ver;
+    int rc_ = carve_scratch(c, [&](Carve &cv) {
+        d_rec = cv.take<double>(S * BP_REC, 64); d_pos = cv.take<double>(3 * S, 64); d_eps = cv.take<double>(S, 64);
+        d_sig = cv.take<double>(S, 64); d_cen = cv.take<double>(3 * K, 64); d_pair = cv.take<i32>(2 * P, 64);
+        d_coef = cv.take<double>(n, 64); d_en = cv.take<double>(P * n, 64); d_ver = cv.take<unsigned char>(3 * P, 64);
+        d_code = cv.take<i32>(P, 64);
+    });
+    if (rc_) return rc_;
     if ((rc_ = copy_to_device(c, d_pos, static_pos, (size_t)S * 24))) return rc_;
     if ((rc_ = copy_to_device(c, d_eps, eps, (size_t)S * 8))) return rc_;
     if ((rc_ = copy_to_device(c, d_sig, sigma, (size_t)S * 8))) return rc_;
     if ((rc_ = copy_to_device(c, d_cen, centers, (size_t)K * 24))) return rc_;
     if ((rc_ = copy_to_device(c, d_pair, pairs, (size_t)P * 8))) return rc_;
     if ((rc_ = copy_to_device(c, d_coef, coeffs, (size_t)n * 8))) return rc_;
-    BrImages I;
+    Images27 I;
     cp_images(c->pbc, I.img);
     k_barrier_atoms<<<dim3((unsigned)((S + BP_BLOCK - 1) / BP_BLOCK)), dim3(BP_BLOCK), 0, c->stream>>>(c->pbc, d_pos, d_eps, d_sig, rc, S, d_rec);
     k_barrier_energies<<<dim3((unsigned)P), dim3(BP_BLOCK), 0, c->stream>>>(c->pbc, pl, I, d_rec, S, d_cen, d_pair, d_coef, (int)n, threshold,

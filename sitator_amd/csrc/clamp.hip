@@ -24,8 +24,8 @@ enum { CL_NEED_NEVER = 0, CL_NEED_ALWAYS = 1, CL_NEED_UNASSIGNED = 2 };
 
 struct ClampArgs {
     Pbc pbc;
-    double img[27][3];
-    const double *pos;             // [frames of the chunk][A][3] or null when no position is needed
+    Images27 img;
+    const double *pos;            // [frames of the chunk][A][3] or null when no position is needed
     double *out;                   // [frames of the chunk][A][3]
     const i64 *labels;             // [F][M] from the chunk's first frame
     const i32 *role;               // [A]
@@ -94,7 +94,7 @@ template <bool VEC2> __global__ __launch_bounds__(CL_TILE) void k_clamp(ClampArg
             else if (a.wrap) { const double *cen = a.sites[lab].center; o[0] = cen[0]; o[1] = cen[1]; o[2] = cen[2]; }
             else {
                 const double p[3] = {tile[3 * t], tile[3 * t + 1], tile[3 * t + 2]};
-                cp_clamp_point(a.pbc, a.img, a.sites[lab], p, o);
+                cp_clamp_point(a.pbc, a.img.img, a.sites[lab], p, o);
             }
         }
         if (!keep) { tile[3 * t] = o[0]; tile[3 * t + 1] = o[1]; tile[3 * t + 2] = o[2]; }
@@ -114,15 +114,6 @@ static i64 clamp_default_workspace()
     const char *e = getenv("SITATOR_CLAMP_WORKSPACE_MB");
     const long long mb = e && *e ? atoll(e) : 0;
     return mb > 0 ? (i64)mb << 20 : CL_DEFAULT_WORKSPACE;
-}
-
-namespace {
-struct ClampBuffers {                       // the two large buffers of a call, returned to the context's pool on every way out
-    sit_ctx *c;
-    double *out = nullptr, *pos = nullptr;
-    explicit ClampBuffers(sit_ctx *c_) : c(c_) {}
-    ~ClampBuffers() { if (out) sit_dfree(c, out); if (pos) sit_dfree(c, pos); }
-};
 }
 
 extern "C" int sit_clamp_trajectory(sit_ctx *c, const double *positions, i64 F, i64 A, const i32 *role, const double *fixed_pos,
@@ -168,18 +159,17 @@ extern "C" int sit_clamp_trajectory(sit_ctx *c, const double *positions, i64 F, 
     const bool vec2 = (Fc == F || ((Fc * A * 3) & 1) == 0) && (host_pos || !any_need || ((size_t)c->d_frames & 15) == 0);
     HIP_TRY(c, hipSetDevice(c->device));
 
-    // small tables in the scratch buffer, every part a multiple of 16 bytes
-    auto up16 = [](i64 b) { return (b + 15) & ~(i64)15; };
-    const i64 o_status = 0, o_sites = 32, o_cen = o_sites + up16(K * (i64)sizeof(ClampSite)), o_fixed = o_cen + up16(K * 24),
-              o_role = o_fixed + up16(A * 24), o_need = o_role + up16(A * 4), total = o_need + up16(A);
-    int rc;
-    if ((rc = ensure_scratch(c, total))) return rc;
-    char *base = (char *)c->d_scratch;
-    u64 *d_status = (u64 *)(base + o_status);
-    ClampSite *d_sites = (ClampSite *)(base + o_sites);
-    double *d_cen = (double *)(base + o_cen), *d_fixed = (double *)(base + o_fixed);
-    i32 *d_role = (i32 *)(base + o_role);
-    unsigned char *d_need = (unsigned char *)(base + o_need);
+    // small tables in the scratch buffer
+    u64 *d_status;
+    ClampSite *d_sites;
+    double *d_cen, *d_fixed;
+    i32 *d_role;
+    unsigned char *d_need;
+    int rc = carve_scratch(c, [&](Carve &cv) {
+        d_status = cv.take<u64>(3); d_sites = cv.take<ClampSite>(K); d_cen = cv.take<double>(3 * K); d_fixed = cv.take<double>(3 * A);
+        d_role = cv.take<i32>(A); d_need = cv.take<unsigned char>(A);
+    });
+    if (rc) return rc;
     u64 *h_status = (u64 *)c->h_pinned;
     h_status[0] = ~0ull; h_status[1] = 0; h_status[2] = 0;
     HIP_TRY(c, hipMemcpyAsync(d_status, h_status, 24, hipMemcpyHostToDevice, c->stream));
@@ -193,20 +183,20 @@ extern "C" int sit_clamp_trajectory(sit_ctx *c, const double *positions, i64 F, 
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));                 // h_status is reused for the read-backs
 
-    ClampBuffers buf(c);
-    HIP_TRY(c, sit_dmalloc(c, (void **)&buf.out, (size_t)(Fc * frame_bytes)));
-    if (host_pos) HIP_TRY(c, sit_dmalloc(c, (void **)&buf.pos, (size_t)(Fc * frame_bytes)));
+    Scoped buf_out(c), buf_pos(c);
+    HIP_TRY(c, sit_dmalloc(c, &buf_out.p, (size_t)(Fc * frame_bytes)));
+    if (host_pos) HIP_TRY(c, sit_dmalloc(c, &buf_pos.p, (size_t)(Fc * frame_bytes)));
     ClampArgs a;
     a.pbc = c->pbc;
-    cp_images(c->pbc, a.img);
-    a.out = buf.out; a.role = d_role; a.need = d_need; a.fixed = d_fixed; a.sites = d_sites; a.status = d_status;
+    cp_images(c->pbc, a.img.img);
+    a.out = (double *)buf_out.p; a.role = d_role; a.need = d_need; a.fixed = d_fixed; a.sites = d_sites; a.status = d_status;
     a.A = A; a.M = M; a.K = K; a.wrap = wrap ? 1 : 0; a.pass = pass_through_unassigned ? 1 : 0;
     for (i64 f0 = 0; f0 < F; f0 += Fc) {
         const i64 nf = f0 + Fc < F ? Fc : F - f0;
         const size_t bytes = (size_t)(nf * frame_bytes);
         if (host_pos) {
-            if ((rc = copy_to_device(c, buf.pos, (const char *)positions + f0 * frame_bytes, bytes))) return rc;
-            a.pos = buf.pos;
+            if ((rc = copy_to_device(c, buf_pos.p, (const char *)positions + f0 * frame_bytes, bytes))) return rc;
+            a.pos = (const double *)buf_pos.p;
         } else {
             a.pos = any_need ? c->d_frames + f0 * A * 3 : nullptr;
         }
@@ -218,15 +208,9 @@ extern "C" int sit_clamp_trajectory(sit_ctx *c, const double *positions, i64 F, 
         t.stop();
         HIP_TRY(c, hipGetLastError());
         HIP_TRY(c, hipMemcpyAsync(h_status, d_status, 24, hipMemcpyDeviceToHost, c->stream));
-        if ((rc = copy_to_host(c, (char *)out + f0 * frame_bytes, buf.out, bytes))) return rc;
+        if ((rc = copy_to_host(c, (char *)out + f0 * frame_bytes, buf_out.p, bytes))) return rc;
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (h_status[1]) return index_out_of_bounds(c, (i64)h_status[1] - 1, K);
-        if (h_status[2]) {
-            char text[128];
-            snprintf(text, sizeof(text), "sit_clamp_trajectory: %llu labels below -1", (unsigned long long)h_status[2]);
-            c->msg = text;
-            return SIT_ERR_INVALID;
-        }
+        if ((rc = label_status(c, "sit_clamp_trajectory", h_status[1], h_status[2], K))) return rc;
         if (h_status[0] != ~0ull) {
             // an ion to clamp is unassigned and nothing passes it through: the smallest index of this chunk is the
             // smallest of all (chunks are taken in frame order)

@@ -44,6 +44,8 @@ template <class P> CP_HD inline void cp_wrap(const P &c, const double p[3], doub
 
 // The 27 image vectors of util/PBCCalculator.pyx:287-295 in the order of the loops (i outermost, k innermost):
 // img[9 i + 3 j + k][d] = (i - 1) cell[0, d] + (j - 1) cell[1, d] + (k - 1) cell[2, d]
+struct Images27 { double img[27][3]; };                             // the table as a kernel argument, passed by value
+
 template <class P> CP_HD inline void cp_images(const P &c, double img[27][3])
 {
     for (int i = 0; i < 3; i++)

@@ -1294,13 +1294,14 @@ static int gram_impl(sit_ctx *c, double *G, u64 *hi, u64 *lo, i64 *seen)
     static const int copies_env = [] { const char *v = getenv("SITATOR_GRAM_COPIES"); const int n = v ? atoi(v) : 0; return n >= 1 && n <= 64 ? n : 0; }();
     int copies = copies_env ? copies_env : 8;
     while (copies > 1 && (copies * DD * 16 > (2LL << 30) || c->N < 4096 * copies)) copies >>= 1;   // small inputs, very large D: fewer
-    const i64 acc = DD * 16 * copies;                                 // [hi copies][lo copies]
-    int rc = ensure_scratch(c, acc + D * 8 + DD * 8 + (c->comm_peer ? DD * 24 : 0));
+    u64 *dhi, *dlo, *ds, *work;                                       // [hi copies], [lo copies], seen; one memset clears the three
+    double *dG;
+    int rc = carve_scratch(c, [&](Carve &cv) {
+        dhi = cv.take<u64>(DD * copies); dlo = cv.take<u64>(DD * copies); ds = cv.take<u64>(D);
+        dG = cv.take<double>(DD); work = cv.take<u64>(c->comm_peer ? 3 * DD : 0);
+    });
     if (rc) return rc;
-    u64 *dhi = (u64 *)c->d_scratch, *dlo = dhi + DD * copies, *ds = dlo + DD * copies;
-    double *dG = (double *)(ds + D);
-    u64 *work = (u64 *)(dG + DD);
-    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, (size_t)(acc + D * 8), c->stream));
+    HIP_TRY(c, hipMemsetAsync(dhi, 0, (size_t)((char *)(ds + D) - (char *)dhi), c->stream));
     StageTimer t(c, T_GRAM);
     const char *runs_env = getenv("SITATOR_RUNS");              // 0: the row-parallel kernels (tests compare the two)
     const bool runs = !(runs_env && atoi(runs_env) == 0) && c->M > 0 && c->N % c->M == 0 && c->N / c->M >= 2;
@@ -1393,13 +1394,12 @@ extern "C" int sit_best_match(sit_ctx *c, const double *cvec, i64 *row_out, doub
     SIT_REQUIRE(c, c->rows_valid && c->N > 0, "sit_best_match: no landmark rows on the device");
     HIP_TRY(c, hipSetDevice(c->device));
     const i64 nb = (c->N + 255) / 256;
-    int rc = ensure_scratch(c, c->D * 8 + nb * 24 + 64);
-    if (rc) return rc;
-    double *dc = (double *)c->d_scratch;
-    double *bv = dc + c->D;
-    i64 *bi = (i64 *)(bv + nb);
-    int *bn = (int *)(bi + nb);
-    double *out2 = (double *)(bn + nb + (nb & 1));
+    double *dc, *bv, *out2;
+    i64 *bi;
+    int *bn;
+    if (int rc = carve_scratch(c, [&](Carve &cv) {
+        dc = cv.take<double>(c->D); bv = cv.take<double>(nb); bi = cv.take<i64>(nb); bn = cv.take<int>(nb); out2 = cv.take<double>(2);
+    })) return rc;
     HIP_TRY(c, hipMemcpyAsync(dc, cvec, (size_t)c->D * 8, hipMemcpyHostToDevice, c->stream));
     k_best_match<<<dim3((unsigned)nb), dim3(256), 0, c->stream>>>(c->d_row_nnz, c->d_row_idx, c->d_row_val, c->N, dc, bv, bi, bn);
     HIP_TRY(c, hipGetLastError());
@@ -1492,13 +1492,14 @@ extern "C" int sit_best_match_groups(sit_ctx *c, const int32_t *group_of_dim, co
     HIP_TRY(c, hipSetDevice(c->device));
     for (i64 d = 0; d < c->D; d++)
         SIT_REQUIRE(c, group_of_dim[d] >= -1 && group_of_dim[d] < G, "sit_best_match_groups: group index out of range");
-    int rc = ensure_scratch(c, c->D * 12 + G * (16 + 24) + 64);
-    if (rc) return rc;
-    double *dc = (double *)c->d_scratch;
-    u64 *keymax = (u64 *)(dc + c->D), *rowmin = keymax + G;
-    i64 *drows = (i64 *)(rowmin + G);
-    double *ddots = (double *)(drows + G), *dnorms = ddots + G;
-    i32 *dg = (i32 *)(dnorms + G);
+    double *dc, *ddots, *dnorms;
+    u64 *keymax, *rowmin;
+    i64 *drows;
+    i32 *dg;
+    if (int rc = carve_scratch(c, [&](Carve &cv) {
+        dc = cv.take<double>(c->D); keymax = cv.take<u64>(G); rowmin = cv.take<u64>(G); drows = cv.take<i64>(G);
+        ddots = cv.take<double>(G); dnorms = cv.take<double>(G); dg = cv.take<i32>(c->D);
+    })) return rc;
     HIP_TRY(c, hipMemcpyAsync(dc, cvec, (size_t)c->D * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dg, group_of_dim, (size_t)c->D * 4, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(keymax, 0, (size_t)G * 8, c->stream));
@@ -1543,12 +1544,13 @@ static int weighted_row_sums_impl(sit_ctx *c, int weighted, i64 K, double *sums,
     SIT_REQUIRE(c, c->rows_valid && c->assign_valid && K > 0, "sit_weighted_row_sums: rows and assignments needed");
     HIP_TRY(c, hipSetDevice(c->device));
     const i64 D = c->D, n = K * D + K;
-    int rc = ensure_scratch(c, n * 24 + (c->comm_peer ? n * 24 : 0));
+    u64 *dhi, *dlo, *work;
+    double *dout;
+    int rc = carve_scratch(c, [&](Carve &cv) {
+        dhi = cv.take<u64>(n); dlo = cv.take<u64>(n); dout = cv.take<double>(n); work = cv.take<u64>(c->comm_peer ? 3 * n : 0);
+    });
     if (rc) return rc;
-    u64 *dhi = (u64 *)c->d_scratch, *dlo = dhi + n;
-    double *dout = (double *)(dlo + n);
-    u64 *work = (u64 *)(dout + n);
-    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, (size_t)(n * 16), c->stream));
+    HIP_TRY(c, hipMemsetAsync(dhi, 0, (size_t)((char *)(dlo + n) - (char *)dhi), c->stream));   // one memset clears both
     const char *runs_env = getenv("SITATOR_RUNS");
     if (c->N > 0 && !(runs_env && atoi(runs_env) == 0) && c->M > 0 && c->N % c->M == 0 && c->N / c->M >= 2) {
         constexpr int NT = 128;

@@ -323,9 +323,8 @@ extern "C" int sit_wrap_points(sit_ctx *c, double *pts, i64 n)
     if (!c || (!pts && n > 0)) return SIT_ERR_INVALID;
     if (n <= 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, n * 24);
-    if (rc) return rc;
-    double *d = (double *)c->d_scratch;
+    double *d;
+    if (int rc = carve_scratch(c, [&](Carve &cv) { d = cv.take<double>(3 * n); })) return rc;
     HIP_TRY(c, hipMemcpyAsync(d, pts, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
     k_wrap_points<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(c->pbc, d, n);
     HIP_TRY(c, hipGetLastError());
@@ -339,9 +338,8 @@ extern "C" int sit_distances(sit_ctx *c, const double *pt1, const double *pts2, 
     if (!c || !pt1 || ((!pts2 || !out) && n > 0)) return SIT_ERR_INVALID;
     if (n <= 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, n * 32);
-    if (rc) return rc;
-    double *d = (double *)c->d_scratch, *o = d + 3 * n;
+    double *d, *o;
+    if (int rc = carve_scratch(c, [&](Carve &cv) { d = cv.take<double>(3 * n); o = cv.take<double>(n); })) return rc;
     HIP_TRY(c, hipMemcpyAsync(d, pts2, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
     k_distances<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream>>>(c->pbc, pt1[0], pt1[1], pt1[2], d, n, o);
     HIP_TRY(c, hipGetLastError());
@@ -365,11 +363,11 @@ extern "C" int sit_site_vertex_distances(sit_ctx *c, const double *centers, cons
     SIT_REQUIRE(c, D > 0 && V > 0 && S > 0, "sit_site_vertex_distances: bad shape");
     for (i64 i = 0; i < D * V; i++) SIT_REQUIRE(c, verts[i] >= -1 && verts[i] < S, "vertex index out of range");
     HIP_TRY(c, hipSetDevice(c->device));
-    const i64 bytes = D * 24 + S * 24 + D * V * 16;
-    int rc = ensure_scratch(c, bytes);
-    if (rc) return rc;
-    double *dc = (double *)c->d_scratch, *dr = dc + 3 * D, *dout = dr + 3 * S;
-    i64 *dv = (i64 *)(dout + D * V);
+    double *dc, *dr, *dout;
+    i64 *dv;
+    if (int rc = carve_scratch(c, [&](Carve &cv) {
+        dc = cv.take<double>(3 * D); dr = cv.take<double>(3 * S); dout = cv.take<double>(D * V); dv = cv.take<i64>(D * V);
+    })) return rc;
     HIP_TRY(c, hipMemcpyAsync(dc, centers, (size_t)D * 24, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dr, ref_static, (size_t)S * 24, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dv, verts, (size_t)(D * V) * 8, hipMemcpyHostToDevice, c->stream));
@@ -417,9 +415,8 @@ extern "C" int sit_average(sit_ctx *c, const double *pts, const double *weights,
     }
     const double off[3] = {c->pbc.cen[0] - pts[3 * about], c->pbc.cen[1] - pts[3 * about + 1],
                            c->pbc.cen[2] - pts[3 * about + 2]};
-    int rc = ensure_scratch(c, n * 32 + 64);
-    if (rc) return rc;
-    double *dp = (double *)c->d_scratch, *dw = dp + 3 * n, *dout = dw + n;
+    double *dp, *dw, *dout;
+    if (int rc = carve_scratch(c, [&](Carve &cv) { dp = cv.take<double>(3 * n); dw = cv.take<double>(n); dout = cv.take<double>(4); })) return rc;
     HIP_TRY(c, hipMemcpyAsync(dp, pts, (size_t)n * 24, hipMemcpyHostToDevice, c->stream));
     if (weights) HIP_TRY(c, hipMemcpyAsync(dw, weights, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
     k_average<<<dim3(1), dim3(256), 0, c->stream>>>(c->pbc, dp, weights ? dw : nullptr, n, off[0], off[1], off[2], dout);

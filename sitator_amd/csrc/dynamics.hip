@@ -13,19 +13,6 @@
 #include "sit_internal.h"
 #include "label_scan.h"
 
-// The layout `lay(Carve &)` of an entry point's scratch: run once to size the buffer, once more to hand out its pieces
-template <class Lay>
-static int carve_scratch(sit_ctx *c, Lay lay)
-{
-    Carve cv = {nullptr, 0};
-    lay(cv);
-    const int rc = ensure_scratch(c, cv.used);
-    if (rc) return rc;
-    cv = {(char *)c->d_scratch, 0};
-    lay(cv);
-    return SIT_OK;
-}
-
 // Step (1) of every scan.  Grid (chunks, ceil(M / 64)).
 __global__ __launch_bounds__(64) void k_label_chunk_summary(const i64 *labels, i64 F, i64 M, int all_known, ChunkSummary *out)
 {
@@ -241,8 +228,7 @@ extern "C" int sit_jump_analysis(sit_ctx *c, i64 K, const i64 *last_known_in, co
     if (time_at_current_out) HIP_TRY(c, hipMemcpyAsync(time_at_current_out, s.out1, (size_t)M * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     *n_problems = (i64)h_np[0];
-    if (h_np[1]) return index_out_of_bounds(c, (i64)h_np[1] - 1, K);
-    return SIT_OK;
+    return label_status(c, "sit_jump_analysis", h_np[1], 0, K);
 }
 
 // ---- assign_to_last_known_site (SiteTrajectory.py:235-304) -----------------------------------------------
@@ -601,7 +587,7 @@ extern "C" int sit_replace_closer(sit_ctx *c, const i64 *records, i64 n, const d
         u64 *h_flags = (u64 *)c->h_pinned;
         HIP_TRY(c, hipMemcpyAsync(h_flags, d_flags, 16, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (h_flags[1]) return index_out_of_bounds(c, (i64)h_flags[1] - 1, K);
+        if ((rc = label_status(c, "sit_replace_closer", h_flags[1], 0, K))) return rc;
         if (h_flags[0]) {
             char text[160];
             snprintf(text, sizeof(text), "sit_replace_closer: %llu records outside the context (ion, frames, sites or position offset)",

@@ -304,13 +304,13 @@ int sample_static_dmax(sit_ctx *c, std::vector<double> &out)
     i64 ns = c->F < 2048 ? c->F : 2048;
     if (ns <= 0) { out.clear(); return SIT_OK; }
     const i64 stride = c->F / ns;
-    int rc = ensure_scratch(c, ns * 8);
-    if (rc) return rc;
+    double *d_max;
+    if (int rc = carve_scratch(c, [&](Carve &cv) { d_max = cv.take<double>(ns); })) return rc;
     k_sample_dmax<<<dim3((unsigned)ns), dim3(256), 0, c->stream>>>(c->pbc, c->d_frames, c->d_static_idx, c->d_ref_static,
-                                                                   c->F, c->A, c->S, stride, (double *)c->d_scratch);
+                                                                   c->F, c->A, c->S, stride, d_max);
     HIP_TRY(c, hipGetLastError());
     out.resize((size_t)ns);
-    HIP_TRY(c, hipMemcpyAsync(out.data(), c->d_scratch, (size_t)ns * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out.data(), d_max, (size_t)ns * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SIT_OK;
 }
@@ -407,11 +407,12 @@ extern "C" int sit_site_counts(sit_ctx *c, i64 K, i64 *counts)
     SIT_SETTLE(c);
     SIT_REQUIRE(c, c->assign_valid && K > 0, "sit_site_counts: no assignments on the device");
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, K * 8);
+    u64 *d_cnt;
+    int rc = carve_scratch(c, [&](Carve &cv) { d_cnt = cv.take<u64>(K); });
     if (rc) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, (size_t)K * 8, c->stream));
-    if ((rc = launch_label_hist(c, c->d_labels, c->N, K, (u64 *)c->d_scratch))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(counts, c->d_scratch, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemsetAsync(d_cnt, 0, (size_t)K * 8, c->stream));
+    if ((rc = launch_label_hist(c, c->d_labels, c->N, K, d_cnt))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(counts, d_cnt, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SIT_OK;
 }
@@ -446,10 +447,12 @@ static int measured_row_width(sit_ctx *c, const sit_fill_params *p, i64 *W_out)
     if ((mode && mode[0] == 'l') || c->rows_overflowed || c->W <= 4 || c->F == 0 || p->dynamic_lattice_mapping || !fill3_eligible(c)) return SIT_OK;
     const i64 Fs = leading_frames(c->M, c->F);
     const i64 Ns = Fs * c->M, W = c->W;
-    int rc = ensure_scratch(c, Ns * (4 + 12 * W) + 64);
+    i32 *s_nnz, *s_idx, *s_max;
+    double *s_val;
+    int rc = carve_scratch(c, [&](Carve &cv) {
+        s_nnz = cv.take<i32>(Ns); s_idx = cv.take<i32>(Ns * W); s_max = cv.take<i32>(2); s_val = cv.take<double>(Ns * W);
+    });
     if (rc) return rc;
-    i32 *s_nnz = (i32 *)c->d_scratch, *s_idx = s_nnz + Ns, *s_max = s_idx + Ns * W;
-    double *s_val = (double *)(((uintptr_t)(s_max + 2) + 15) & ~(uintptr_t)15);
     // the context points at the scratch rows while the leading frames are filled
     i32 *k_nnz = c->d_row_nnz, *k_idx = c->d_row_idx;
     double *k_val = c->d_row_val;
@@ -906,12 +909,12 @@ extern "C" int sit_static_seen(sit_ctx *c, i64 local_frame, uint8_t *seen)
     if (!c || !seen) return SIT_ERR_INVALID;
     SIT_REQUIRE(c, c->d_frames && local_frame >= 0 && local_frame < c->F, "sit_static_seen: bad frame");
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, c->S + 64);
-    if (rc) return rc;
+    unsigned char *d_seen;
+    if (int rc = carve_scratch(c, [&](Carve &cv) { d_seen = cv.take<unsigned char>(c->S); })) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_err, 0xFF, sizeof(u64), c->stream));
     MapArgs m;
     m.P = c->pbc; m.frames = c->d_frames; m.static_idx = c->d_static_idx; m.ref_static = c->d_ref_static;
-    m.lattice_map = nullptr; m.err = c->d_err; m.seen_out = (unsigned char *)c->d_scratch;
+    m.lattice_map = nullptr; m.err = c->d_err; m.seen_out = d_seen;
     m.frame_dmax_bits = nullptr;
     m.F = c->F; m.A = c->A; m.S = c->S; m.M = c->M; m.frame0 = c->frame0; m.only_frame = local_frame;
     m.relaxed = 1; m.static_thr = c->static_thr;
@@ -919,7 +922,7 @@ extern "C" int sit_static_seen(sit_ctx *c, i64 local_frame, uint8_t *seen)
     HIP_TRY(c, hipFuncSetAttribute((const void *)k_lattice_map, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     k_lattice_map<<<dim3(1), dim3(256), lds, c->stream>>>(m);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(seen, c->d_scratch, (size_t)c->S, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(seen, d_seen, (size_t)c->S, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SIT_OK;
 }
@@ -950,13 +953,13 @@ extern "C" int sit_get_rows_dense(sit_ctx *c, i64 row0, i64 nrows, double *out)
     SIT_REQUIRE(c, c->rows_valid && row0 >= 0 && nrows >= 0 && row0 + nrows <= c->N, "sit_get_rows_dense: bad range or no rows");
     if (nrows == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, nrows * c->D * 8);
-    if (rc) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->d_scratch, 0, (size_t)(nrows * c->D * 8), c->stream));
+    double *d_out;
+    if (int rc = carve_scratch(c, [&](Carve &cv) { d_out = cv.take<double>(nrows * c->D); })) return rc;
+    HIP_TRY(c, hipMemsetAsync(d_out, 0, (size_t)(nrows * c->D * 8), c->stream));
     k_rows_dense<<<dim3((unsigned)((nrows + 255) / 256)), dim3(256), 0, c->stream>>>(
-        c->d_row_nnz, c->d_row_idx, c->d_row_val, c->N, c->D, row0, nrows, (double *)c->d_scratch);
+        c->d_row_nnz, c->d_row_idx, c->d_row_val, c->N, c->D, row0, nrows, d_out);
     HIP_TRY(c, hipGetLastError());
-    HIP_TRY(c, hipMemcpyAsync(out, c->d_scratch, (size_t)(nrows * c->D * 8), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(out, d_out, (size_t)(nrows * c->D * 8), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SIT_OK;
 }

@@ -50,12 +50,6 @@ void drop_buffers(sit_ctx *c, GroupState *g)
     g->valid = false;
 }
 
-struct Scoped {                                                  // a buffer of one call, back to the pool on every way out
-    sit_ctx *c;
-    void *p = nullptr;
-    explicit Scoped(sit_ctx *c_) : c(c_) {}
-    ~Scoped() { if (p) sit_dfree(c, p); }
-};
 }
 
 void group_free(sit_ctx *c)
@@ -205,7 +199,7 @@ extern "C" int sit_group_by_site(sit_ctx *c, const double *positions, i64 F, i64
         SIT_REQUIRE(c, A == c->A, "sit_group_by_site: A is not the number of atoms of the resident frames");
     }
     const i64 N = F * M;
-    const GroupPlan p = gp_plan(N, K, M);
+    GroupPlan p = gp_plan(N, K, M);
     if (!p.ok) { c->msg = "sit_group_by_site: more than 2^31 entries, or a chunk x site table beyond 8 GB"; return SIT_ERR_CAPACITY; }
     const i64 Fs = host_pos ? gp_frames_per_stage(workspace_bytes, F, A) : F;
     SIT_REQUIRE(c, !host_pos || F == 0 || A == 0 || Fs >= 1, "sit_group_by_site: the workspace cap is below one frame");
@@ -216,41 +210,30 @@ extern "C" int sit_group_by_site(sit_ctx *c, const double *positions, i64 F, i64
     g->offsets.assign((size_t)K + 1, 0);
     g->N = 0; g->K = K; g->n_chunks = p.n_chunks; g->lds = p.lds; g->recenter_next = 0; g->recenter_n = 0;
 
-    int rc;
-    if ((rc = ensure_scratch(c, p.scratch_bytes))) return rc;
-    char *base = (char *)c->d_scratch;
-    u64 *d_status = (u64 *)(base + p.o_status);
-    i64 *d_totals = (i64 *)(base + p.o_totals), *d_off = (i64 *)(base + p.o_offsets);
-    i32 *d_midx = (i32 *)(base + p.o_midx);
-    unsigned *d_table = (unsigned *)(base + p.o_table);
+    int rc = carve_scratch(c, [&](Carve &cv) { p.lay(cv); });
+    if (rc) return rc;
     const size_t lds_bytes = p.lds ? (size_t)(K > 0 ? K : 1) * 4 : 0;
     const dim3 cgrid((unsigned)(p.n_chunks > 0 ? p.n_chunks : 1));
 
     HIP_TRY(c, hipEventRecord(g->ev0, c->stream));
-    HIP_TRY(c, hipMemsetAsync(d_status, 0, 32, c->stream));
+    HIP_TRY(c, hipMemsetAsync(p.status, 0, 32, c->stream));
     std::vector<i64> totals((size_t)K, 0);
     if (p.n_chunks > 0 && K > 0) {
-        if (!p.lds) HIP_TRY(c, hipMemsetAsync(d_table, 0, (size_t)p.table_words * 4, c->stream));
-        if (p.lds) k_group_hist<true><<<cgrid, dim3(GP_TILE), lds_bytes, c->stream>>>(c->d_labels, N, K, d_table, d_status);
-        else k_group_hist<false><<<cgrid, dim3(GP_TILE), 0, c->stream>>>(c->d_labels, N, K, d_table, d_status);
-        k_group_scan<<<dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream>>>(d_table, p.n_chunks, K, d_totals);
+        if (!p.lds) HIP_TRY(c, hipMemsetAsync(p.table, 0, (size_t)p.table_words * 4, c->stream));
+        if (p.lds) k_group_hist<true><<<cgrid, dim3(GP_TILE), lds_bytes, c->stream>>>(c->d_labels, N, K, p.table, p.status);
+        else k_group_hist<false><<<cgrid, dim3(GP_TILE), 0, c->stream>>>(c->d_labels, N, K, p.table, p.status);
+        k_group_scan<<<dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream>>>(p.table, p.n_chunks, K, p.totals);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(totals.data(), d_totals, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(totals.data(), p.totals, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
     } else if (p.n_chunks > 0) {
         // no site at all: the labels are still looked at (every assigned one is beyond the sites)
-        k_group_hist<true><<<cgrid, dim3(GP_TILE), lds_bytes, c->stream>>>(c->d_labels, N, K, d_table, d_status);
+        k_group_hist<true><<<cgrid, dim3(GP_TILE), lds_bytes, c->stream>>>(c->d_labels, N, K, p.table, p.status);
         HIP_TRY(c, hipGetLastError());
     }
     u64 *h_status = (u64 *)c->h_pinned;
-    HIP_TRY(c, hipMemcpyAsync(h_status, d_status, 16, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(h_status, p.status, 16, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    if (h_status[0]) return index_out_of_bounds(c, (i64)h_status[0] - 1, K);
-    if (h_status[1]) {
-        char text[128];
-        snprintf(text, sizeof(text), "sit_group_by_site: %llu labels below -1", (unsigned long long)h_status[1]);
-        c->msg = text;
-        return SIT_ERR_INVALID;
-    }
+    if ((rc = label_status(c, "sit_group_by_site", h_status[0], h_status[1], K))) return rc;
     for (i64 s = 0; s < K; s++) g->offsets[(size_t)s + 1] = g->offsets[(size_t)s] + totals[(size_t)s];
     const i64 Ng = g->offsets[(size_t)K];
     if (Ng > N) { c->msg = "sit_group_by_site: the site counts exceed the entries"; return SIT_ERR_CAPACITY; }
@@ -262,16 +245,16 @@ extern "C" int sit_group_by_site(sit_ctx *c, const double *positions, i64 F, i64
     HIP_TRY(c, sit_dmalloc(c, (void **)&g->d_offsets, ((size_t)K + 1) * 8));
     HIP_TRY(c, sit_dmalloc(c, (void **)&g->d_shift, (size_t)(K > 0 ? K : 1) * 24));
     HIP_TRY(c, hipMemcpyAsync(g->d_offsets, g->offsets.data(), ((size_t)K + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_off, g->offsets.data(), ((size_t)K + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (host_pos && M > 0) HIP_TRY(c, hipMemcpyAsync(d_midx, m32.data(), (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(p.offsets, g->offsets.data(), ((size_t)K + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (host_pos && M > 0) HIP_TRY(c, hipMemcpyAsync(p.midx, m32.data(), (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
 
     if (Ng > 0) {
         Scoped dest(c), stage(c);
         HIP_TRY(c, sit_dmalloc(c, &dest.p, (size_t)N * 4));
         if (p.lds) k_group_scatter<true><<<cgrid, dim3(GP_TILE), lds_bytes, c->stream>>>(
-            c->d_labels, c->d_confs, N, K, p.label_bits, d_table, d_off, Ng, (unsigned *)dest.p, g->confs, g->entries);
+            c->d_labels, c->d_confs, N, K, p.label_bits, p.table, p.offsets, Ng, (unsigned *)dest.p, g->confs, g->entries);
         else k_group_scatter<false><<<cgrid, dim3(GP_TILE), 0, c->stream>>>(
-            c->d_labels, c->d_confs, N, K, p.label_bits, d_table, d_off, Ng, (unsigned *)dest.p, g->confs, g->entries);
+            c->d_labels, c->d_confs, N, K, p.label_bits, p.table, p.offsets, Ng, (unsigned *)dest.p, g->confs, g->entries);
         HIP_TRY(c, hipGetLastError());
         if (!host_pos) {
             k_group_positions<<<dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream>>>(
@@ -286,7 +269,7 @@ extern "C" int sit_group_by_site(sit_ctx *c, const double *positions, i64 F, i64
                 if ((rc = copy_to_device(c, stage.p, (const char *)positions + f0 * frame_bytes, (size_t)(nf * frame_bytes)))) return rc;
                 const i64 e_lo = f0 * M, e_hi = (f0 + nf) * M;
                 k_group_positions<<<dim3((unsigned)((e_hi - e_lo + 255) / 256)), dim3(256), 0, c->stream>>>(
-                    (const double *)stage.p, A, d_midx, M, e_lo, e_hi, f0, (const unsigned *)dest.p, Ng, g->pts);
+                    (const double *)stage.p, A, p.midx, M, e_lo, e_hi, f0, (const unsigned *)dest.p, Ng, g->pts);
                 HIP_TRY(c, hipGetLastError());
                 HIP_TRY(c, hipStreamSynchronize(c->stream));
             }
@@ -405,9 +388,9 @@ extern "C" int sit_grouped_bucket_averages(sit_ctx *c, i64 n_avg, int weighted, 
     SIT_REQUIRE(c, B < ((i64)1 << 31), "sit_grouped_bucket_averages: more than 2^31 buckets");
     if (B == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = ensure_scratch(c, B * 32))) return rc;
-    double *d_out = (double *)c->d_scratch;
-    i64 *d_anchor = (i64 *)(d_out + 3 * B);
+    double *d_out;
+    i64 *d_anchor;
+    if ((rc = carve_scratch(c, [&](Carve &cv) { d_out = cv.take<double>(3 * B); d_anchor = cv.take<i64>(B); }))) return rc;
     HIP_TRY(c, hipEventRecord(g->ev0, c->stream));
     k_group_bucket_avg<<<dim3((unsigned)B), dim3(GA_BLOCK), 0, c->stream>>>(c->pbc, g->pts, g->confs, g->d_offsets, n_avg, weighted ? 1 : 0,
                                                                            d_out, d_anchor);

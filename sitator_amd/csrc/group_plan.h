@@ -14,6 +14,8 @@
 
 #include <stdint.h>
 
+#include "scratch_carve.h"
+
 #define GP_TILE 64
 #define GP_CHUNK 4096                                  // entries per chunk: 64 tiles
 #define GP_LDS_MAX_SITES 8192                          // cursors of 4 bytes: 32 KB of LDS
@@ -22,16 +24,23 @@
 #define GP_DEFAULT_WORKSPACE ((int64_t)1 << 30)        // staged frames of a host trajectory
 
 struct GroupPlan {
-    int64_t n_entries, n_sites, n_chunks;
+    int64_t n_entries, n_sites, n_mobile, n_chunks;
     int lds;                                           // 1: a wave's row of the table lives in LDS
     int label_bits;                                    // bits that tell the labels [0, n_sites) apart
     int64_t table_words;                               // n_chunks * n_sites (uint32)
-    // byte offsets in the scratch buffer, each a multiple of 16
-    int64_t o_status, o_totals, o_offsets, o_midx, o_table, scratch_bytes;
     int ok;                                            // 0: beyond GP_MAX_ENTRIES or GP_MAX_TABLE_BYTES
+    // the small tables in the scratch buffer: status words (32 bytes), totals [n_sites], offsets [n_sites + 1], the mobile
+    // columns [n_mobile], the table
+    unsigned long long *status;
+    int64_t *totals, *offsets;
+    int32_t *midx;
+    unsigned *table;
+    void lay(Carve &cv)
+    {
+        status = cv.take<unsigned long long>(4); totals = cv.take<int64_t>(n_sites); offsets = cv.take<int64_t>(n_sites + 1);
+        midx = cv.take<int32_t>(n_mobile); table = cv.take<unsigned>(table_words);
+    }
 };
-
-static inline int64_t gp_up16(int64_t b) { return (b + 15) & ~(int64_t)15; }
 
 static inline int gp_label_bits(int64_t n_sites)
 {
@@ -52,19 +61,14 @@ static inline int64_t gp_chunk_end(const GroupPlan &p, int64_t chunk)
 static inline GroupPlan gp_plan(int64_t n_entries, int64_t n_sites, int64_t n_mobile)
 {
     GroupPlan p;
-    p.n_entries = n_entries; p.n_sites = n_sites;
+    p.n_entries = n_entries; p.n_sites = n_sites; p.n_mobile = n_mobile;
     p.n_chunks = (n_entries + GP_CHUNK - 1) / GP_CHUNK;
     p.lds = n_sites <= GP_LDS_MAX_SITES ? 1 : 0;
     p.label_bits = gp_label_bits(n_sites);
     p.ok = n_entries >= 0 && n_sites >= 0 && n_mobile >= 0 && n_entries <= GP_MAX_ENTRIES && n_sites < ((int64_t)1 << 31)
            && (p.n_chunks == 0 || n_sites == 0 || n_sites <= GP_MAX_TABLE_BYTES / 4 / p.n_chunks);
     p.table_words = p.ok ? p.n_chunks * n_sites : 0;
-    p.o_status = 0;
-    p.o_totals = 32;
-    p.o_offsets = p.o_totals + gp_up16(n_sites * 8);
-    p.o_midx = p.o_offsets + gp_up16((n_sites + 1) * 8);
-    p.o_table = p.o_midx + gp_up16(n_mobile * 4);
-    p.scratch_bytes = p.o_table + gp_up16(p.table_words * 4);
+    p.status = nullptr; p.totals = p.offsets = nullptr; p.midx = nullptr; p.table = nullptr;
     return p;
 }
 

@@ -171,12 +171,13 @@ extern "C" int sit_grouped_hull_volumes(sit_ctx *c, double *volumes, int32_t *st
     if (g.K == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const i64 K = g.K, N = g.N;
-    const i64 o_status = (K * 8 + 15) & ~(i64)15, o_facets = o_status + ((K * 4 + 15) & ~(i64)15), o_mask = o_facets + ((K * 4 + 15) & ~(i64)15);
-    if ((rc = ensure_scratch(c, o_mask + (N > 0 ? N : 1)))) return rc;
-    char *base = (char *)c->d_scratch;
-    double *d_vol = (double *)base;
-    i32 *d_status = (i32 *)(base + o_status), *d_facets = (i32 *)(base + o_facets);
-    unsigned char *d_mask = (unsigned char *)(base + o_mask);
+    double *d_vol;
+    i32 *d_status, *d_facets;
+    unsigned char *d_mask;
+    rc = carve_scratch(c, [&](Carve &cv) {
+        d_vol = cv.take<double>(K); d_status = cv.take<i32>(K); d_facets = cv.take<i32>(K); d_mask = cv.take<unsigned char>(N > 0 ? N : 1);
+    });
+    if (rc) return rc;
     HIP_TRY(c, hipMemsetAsync(d_mask, 0, (size_t)(N > 0 ? N : 1), c->stream));
     HIP_TRY(c, hipEventRecord(g.ev0, c->stream));
     k_group_hull<<<dim3((unsigned)K), dim3(HP_BLOCK), 0, c->stream>>>(g.work, g.d_offsets, d_vol, d_status, d_facets, d_mask);

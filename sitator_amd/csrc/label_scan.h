@@ -8,6 +8,8 @@
 
 #include <stdint.h>
 
+#include "scratch_carve.h"
+
 #ifdef __HIPCC__
 #define LS_HD __host__ __device__
 #else
@@ -105,19 +107,7 @@ LS_HD inline AlkStep alk_step(AlkState &s, i64 cur, i64 threshold)
     return o;
 }
 
-// ---- scratch carver: a layout is written once, as the takes it makes; run on a null base it sizes the buffer (`used`),
-//      run on the buffer it hands out the pointers - the byte count and the pointers cannot disagree.
-struct Carve {
-    char *base;
-    i64 used;
-    template <class T> T *take(i64 n)                            // n <= 0: no bytes (the pointer is the next take's)
-    {
-        T *p = base ? (T *)(base + used) : nullptr;
-        used += ((n > 0 ? n : 0) * (i64)sizeof(T) + 15) & ~(i64)15;
-        return p;
-    }
-};
-
+// ---- the scratch layouts of the scans (the carver: scratch_carve.h)
 // What the three launches of a forward scan share: the state carried in and out per ion (the jump scan uses the first
 // array of each), the summaries, and the state at every chunk's start (S: i64, JaState, AlkState).
 template <class S>

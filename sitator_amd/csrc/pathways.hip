@@ -15,15 +15,6 @@
 #define PW_BLOCK 256
 
 namespace {
-struct PwImages { double img[27][3]; };                          // by value: kernel arguments, read with scalar loads
-
-struct PwScoped {                                                // a buffer of one call, back to the pool on every way out
-    sit_ctx *c;
-    void *p = nullptr;
-    explicit PwScoped(sit_ctx *c_) : c(c_) {}
-    ~PwScoped() { if (p) sit_dfree(c, p); }
-};
-
 __device__ __forceinline__ int label_load(const i32 *label, int x)
 {
     return __hip_atomic_load(label + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -35,7 +26,7 @@ inline unsigned blocks_for(i64 n) { return (unsigned)((n + PW_BLOCK - 1) / PW_BL
 // ---- the edge pass ----------------------------------------------------------------------------------------------------------
 
 // entry e = from * K + to of the K x K mask: code[e] = the image code of a connected pair, 0 elsewhere; *count += connected
-__global__ __launch_bounds__(PW_BLOCK) void k_pw_codes(PwImages I, const unsigned char *conn, const double *centers, i64 K, i32 *code,
+__global__ __launch_bounds__(PW_BLOCK) void k_pw_codes(Images27 I, const unsigned char *conn, const double *centers, i64 K, i32 *code,
                                                        unsigned *count)
 {
     const i64 e = (i64)blockIdx.x * PW_BLOCK + threadIdx.x;
@@ -128,22 +119,22 @@ extern "C" int sit_pathway_components(sit_ctx *c, i64 K, const uint8_t *conn, co
     if (K == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
     const i64 KK = K * K, n_nodes = (i64)n_images * K;
-    // scratch: 4 words {connected entries, list cursor, change flag, -} | labels | codes | centres | mask
-    const i64 o_label = 64, o_code = o_label + ((n_nodes * 4 + 63) & ~(i64)63), o_cen = o_code + ((KK * 4 + 63) & ~(i64)63);
-    const i64 o_conn = o_cen + ((K * 24 + 63) & ~(i64)63);
-    int rc;
-    if ((rc = ensure_scratch(c, o_conn + KK))) return rc;
-    char *base = (char *)c->d_scratch;
-    unsigned *d_words = (unsigned *)base;
-    i32 *d_label = (i32 *)(base + o_label), *d_code = (i32 *)(base + o_code);
-    double *d_cen = (double *)(base + o_cen);
-    unsigned char *d_conn = (unsigned char *)(base + o_conn);
+    // scratch, every piece on a 64-byte boundary: 16 words {connected entries, list cursor, change flag, -} | labels | codes | centres | mask
+    unsigned *d_words;
+    i32 *d_label, *d_code;
+    double *d_cen;
+    unsigned char *d_conn;
+    int rc = carve_scratch(c, [&](Carve &cv) {
+        d_words = cv.take<unsigned>(16, 64); d_label = cv.take<i32>(n_nodes, 64); d_code = cv.take<i32>(KK, 64);
+        d_cen = cv.take<double>(3 * K, 64); d_conn = cv.take<unsigned char>(KK, 64);
+    });
+    if (rc) return rc;
     unsigned *h_words = (unsigned *)c->h_pinned;
 
     if ((rc = copy_to_device(c, d_conn, conn, (size_t)KK))) return rc;
     if ((rc = copy_to_device(c, d_cen, centers, (size_t)K * 24))) return rc;
     HIP_TRY(c, hipMemsetAsync(d_words, 0, 64, c->stream));
-    PwImages I;
+    Images27 I;
     cp_images(c->pbc, I.img);
     k_pw_codes<<<dim3(blocks_for(KK)), dim3(PW_BLOCK), 0, c->stream>>>(I, d_conn, d_cen, K, d_code, d_words);
     k_pw_init<<<dim3(blocks_for(n_nodes)), dim3(PW_BLOCK), 0, c->stream>>>(d_label, n_nodes);
@@ -153,7 +144,7 @@ extern "C" int sit_pathway_components(sit_ctx *c, i64 K, const uint8_t *conn, co
     const i64 n_edges = (i64)h_words[0];
     if (n_edges > KK) { c->msg = "sit_pathway_components: more connected pairs counted than the mask has entries"; return SIT_ERR_CAPACITY; }
 
-    PwScoped list(c);
+    Scoped list(c);
     i64 taken = 0;
     if (n_edges > 0) {
         HIP_TRY(c, sit_dmalloc(c, &list.p, (size_t)n_edges * 12));
@@ -187,7 +178,7 @@ extern "C" int sit_pathway_components(sit_ctx *c, i64 K, const uint8_t *conn, co
 
 // ---- PBCCalculator.min_image (util/PBCCalculator.pyx:262-316) for n pairs -------------------------------------------------
 
-__global__ __launch_bounds__(PW_BLOCK) void k_pw_min_image(PwImages I, const double *ref, double *pts, i64 n, i32 *code)
+__global__ __launch_bounds__(PW_BLOCK) void k_pw_min_image(Images27 I, const double *ref, double *pts, i64 n, i32 *code)
 {
     const i64 p = (i64)blockIdx.x * PW_BLOCK + threadIdx.x;
     if (p >= n) return;
@@ -206,13 +197,13 @@ extern "C" int sit_min_image(sit_ctx *c, const double *ref, double *pts, i64 n, 
     SIT_REQUIRE(c, n < ((i64)1 << 31), "sit_min_image: more than 2^31 pairs");
     if (n == 0) return SIT_OK;
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure_scratch(c, n * 52))) return rc;
-    double *d_ref = (double *)c->d_scratch, *d_pts = d_ref + 3 * n;
-    i32 *d_code = (i32 *)(d_pts + 3 * n);
+    double *d_ref, *d_pts;
+    i32 *d_code;
+    int rc = carve_scratch(c, [&](Carve &cv) { d_ref = cv.take<double>(3 * n); d_pts = cv.take<double>(3 * n); d_code = cv.take<i32>(n); });
+    if (rc) return rc;
     if ((rc = copy_to_device(c, d_ref, ref, (size_t)n * 24))) return rc;
     if ((rc = copy_to_device(c, d_pts, pts, (size_t)n * 24))) return rc;
-    PwImages I;
+    Images27 I;
     cp_images(c->pbc, I.img);
     k_pw_min_image<<<dim3(blocks_for(n)), dim3(PW_BLOCK), 0, c->stream>>>(I, d_ref, d_pts, n, d_code);
     HIP_TRY(c, hipGetLastError());

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "sitator_hip.h"
+#include "scratch_carve.h"
 
 typedef int64_t i64;
 typedef int32_t i32;
@@ -235,11 +236,45 @@ static inline int ensure_scratch(sit_ctx *c, i64 bytes)
     return SIT_OK;
 }
 
+// The layout `lay(Carve &)` of an entry point's scratch: run once to size the buffer, once more to hand out its pieces
+template <class Lay>
+static int carve_scratch(sit_ctx *c, Lay lay)
+{
+    Carve cv = {nullptr, 0};
+    lay(cv);
+    const int rc = ensure_scratch(c, cv.used);
+    if (rc) return rc;
+    cv = {(char *)c->d_scratch, 0};
+    lay(cv);
+    return SIT_OK;
+}
+
+// a pool buffer of one call, back to the pool on every way out
+struct Scoped {
+    sit_ctx *c;
+    void *p = nullptr;
+    explicit Scoped(sit_ctx *c_) : c(c_) {}
+    Scoped(const Scoped &) = delete;
+    ~Scoped() { if (p) sit_dfree(c, p); }
+};
+
 // numpy's IndexError text for a site index beyond a table of K sites (_lib.py matches on its first word)
 static inline int index_out_of_bounds(sit_ctx *c, i64 index, i64 K)
 {
     char text[128];
     snprintf(text, sizeof(text), "index %lld is out of bounds for axis 0 with size %lld", (long long)index, (long long)K);
+    c->msg = text;
+    return SIT_ERR_INVALID;
+}
+
+// the two status words of a kernel that looked at labels before indexing with them: the largest label beyond the K sites,
+// + 1 (0: none), and the number of labels below -1 (0 where the entry point counts none)
+static inline int label_status(sit_ctx *c, const char *who, u64 beyond_plus_1, u64 below, i64 K)
+{
+    if (beyond_plus_1) return index_out_of_bounds(c, (i64)beyond_plus_1 - 1, K);
+    if (!below) return SIT_OK;
+    char text[128];
+    snprintf(text, sizeof(text), "%s: %llu labels below -1", who, (unsigned long long)below);
     c->msg = text;
     return SIT_ERR_INVALID;
 }

@@ -158,10 +158,9 @@ extern "C" int sit_site_anchors(sit_ctx *c, int weighted, i64 K, double *wmax, i
     SIT_SETTLE(c);
     SIT_REQUIRE(c, c->assign_valid && c->d_frames && K > 0, "sit_site_anchors: assignments and frames needed");
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, K * (8 + 8 + 24));
-    if (rc) return rc;
-    u64 *dw = (u64 *)c->d_scratch, *df = dw + K;
-    double *dp = (double *)(df + K);
+    u64 *dw, *df;
+    double *dp;
+    if (int rc = carve_scratch(c, [&](Carve &cv) { dw = cv.take<u64>(K); df = cv.take<u64>(K); dp = cv.take<double>(3 * K); })) return rc;
     const i64 row_offset = c->frame0 * c->M;
     HIP_TRY(c, hipMemsetAsync(dw, 0, (size_t)K * 8, c->stream));
     HIP_TRY(c, hipMemsetAsync(df, 0xFF, (size_t)K * 8, c->stream));
@@ -201,9 +200,8 @@ extern "C" int sit_site_sums(sit_ctx *c, int weighted, i64 K, const double *anch
     rpb = (rpb + 255) / 256 * 256;
     if (rpb < 4096) rpb = 4096;
     const i64 nblocks = c->N > 0 ? (c->N + rpb - 1) / rpb : 0;
-    int rc = ensure_scratch(c, K * (24 + 32) + nblocks * K * 32);
-    if (rc) return rc;
-    double *da = (double *)c->d_scratch, *ds = da + 3 * K, *dp = ds + 4 * K;
+    double *da, *ds, *dp;
+    if (int rc = carve_scratch(c, [&](Carve &cv) { da = cv.take<double>(3 * K); ds = cv.take<double>(4 * K); dp = cv.take<double>(nblocks * K * 4); })) return rc;
     HIP_TRY(c, hipMemcpyAsync(da, anchor_pts, (size_t)K * 24, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(ds, 0, (size_t)K * 32, c->stream));
     StageTimer t(c, T_CENTERS);
@@ -346,9 +344,8 @@ extern "C" int sit_cooccupancy(sit_ctx *c, i64 K, uint8_t *co)
     SIT_REQUIRE(c, c->assign_valid && K > 0, "sit_cooccupancy: assignments needed");
     SIT_REQUIRE(c, K <= CO_MAX_SITES, "sit_cooccupancy: more than 16384 sites (the K x K matrix is limited to 256 MB)");
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc = ensure_scratch(c, K * K);
-    if (rc) return rc;
-    unsigned char *d_co = (unsigned char *)c->d_scratch;
+    unsigned char *d_co;
+    if (int rc = carve_scratch(c, [&](Carve &cv) { d_co = cv.take<unsigned char>(K * K); })) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_err, 0xFF, sizeof(u64), c->stream));
     HIP_TRY(c, hipMemsetAsync(d_co, 0, (size_t)(K * K), c->stream));
     StageTimer t(c, T_OCC);

@@ -225,6 +225,7 @@ GROUPINGS = {
     "many": [("gaussian", 8, s) for s in range(600)],
     "shell": [("shell", 600, 0)],
     "doubled": [("doubled", 130, 0), ("doubled", 8, 1)],
+    "small": [("gaussian", 4, 3), ("interior5", 5, 1), ("gaussian", 4, 4)],            # 3 sites over 13 points
 }
 FLAGGED_SITES = [("cube", 8, 0, FLAGGED), ("three", 3, 0, FEW), ("coplanar", 40, 0, FLAGGED), ("shell", 1100, 1, CAPACITY)]
 

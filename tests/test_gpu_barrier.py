@@ -22,6 +22,8 @@ CELLS = {"cubic": BR.CUBIC, "cubic4": np.eye(3) * 4.0, "triclinic": BR.TRICLINIC
 # (cell, rc / smallest height, S, n, P, atoms given outside the cell)
 RAW = [
     ("cubic", 0.45, 1, 3, 1, False),
+    ("cubic", 0.45, 3, 3, 1, False),
+    ("cubic", 0.45, 3, 3, 3, False),
     ("cubic", 0.45, 63, 4, 2, False),
     ("cubic", 0.45, 64, 5, 1, False),
     ("cubic", 0.45, 65, 67, 2, True),

@@ -135,8 +135,13 @@ def _nobody_assigned():
     return np.full((BLOCK + 3, 5), -1, dtype=np.int64), 9, []
 
 
+def _three_sites():
+    lab = np.array([[0, 1], [2, -1], [2, 2]])
+    return lab, 3, [(0, 1, True), (1, 0, True), (2, 2, True), (0, 2, False), (1, 2, False), (0, 0, True)]
+
+
 HAND_BUILT = [_only_frame_0, _newcomer_from_unknown, _changes_on_block_starts, _two_ions_on_one_site,
-              _an_ion_never_assigned, _nobody_assigned]
+              _an_ion_never_assigned, _nobody_assigned, _three_sites]
 
 
 @pytest.mark.parametrize("case", HAND_BUILT, ids=[c.__name__.strip("_") for c in HAND_BUILT])

@@ -89,11 +89,11 @@ def assert_grouping(ctx, offsets, want, what=""):
 
 def grouping_shapes():
     c = chunk()
-    return [(1, 1, 1), (3, 7, 3), (5, 65, 30)] + [shape_for(n) + (5,) for n in (c - 1, c, c + 1)] + [(200, 70, 9)]
+    return [(1, 1, 1), (3, 7, 3), (5, 65, 30)] + [shape_for(n) + (5,) for n in (c - 1, c, c + 1)] + [(200, 70, 9), (3, 3, 5)]
 
 
 @pytest.mark.parametrize("layout", ["first", "last", "interleaved"])
-@pytest.mark.parametrize("case", range(7))
+@pytest.mark.parametrize("case", range(8))
 def test_grouping_against_restatement(case, layout):
     F, M, K = grouping_shapes()[case]
     labels, pos, confs = GR.designed(CELL, F, M, K, seed=F + M, n_unknown=F * M // 9, consumers=False)
@@ -312,7 +312,7 @@ def bucket_case(n, seed, big):
         seed += 1000
 
 
-@pytest.mark.parametrize("n", [2, 4])
+@pytest.mark.parametrize("n", [2, 3, 4])                          # 3: an odd number of buckets
 def test_bucket_averages_anchor_exact_and_mean_within_the_derived_bound(n):
     labels, pos, confs, off, pts, cf = bucket_case(n, seed=n, big=3000)
     K = len(off) - 1

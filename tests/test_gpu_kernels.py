@@ -457,6 +457,7 @@ def test_frames_beyond_sampled_displacement_fall_back_and_match_oracle(oracle):
     assert rc == 0
     lo, n = 30 * 64, 12 * 64
     mine = ctx.rows_dense(lo, n)
+    assert np.array_equal(ctx.rows_dense(lo + 1, 3), mine[1:4])
     wrapped = oracle.wrap_points(host.cell, frames[30:42])
     verts, vcd = oracle.site_vertex_distances(host.cell, host.centers, host.vertices, ref[sm])
     exp, _ = oracle.fill(host.cell, wrapped, np.where(sm)[0], np.where(mm)[0], ref[sm], verts, vcd)

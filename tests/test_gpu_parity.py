@@ -426,3 +426,41 @@ def test_integration_md_binding_fills_the_reference_golden(monkeypatch):
     assert lib.sit_fill(h, C.byref(p), C.byref(nz), C.byref(err)) == 1
     assert b"struct_size" in lib.sit_last_message(h)
     lib.sit_destroy(h)
+
+
+@pytest.mark.parametrize("n", [1, 3, 5])
+def test_pbc_surface_on_a_few_points(n):
+    """wrap_points, distances and average at counts where every piece of the call's scratch layout ends off a 16-byte
+    boundary, against the CPU oracle (the bars of test_pbc_surface_against_reference)."""
+    from oracle import oracle
+    from sitator_amd import PBCCalculator
+    cell = G.load("pbc_known_answers")["tri/cell"]
+    rng = np.random.default_rng(70 + n)
+    pts = (rng.random((n, 3)) * 3.0 - 1.0) @ cell             # up to a cell outside on either side
+    pt1, w = rng.random(3) @ cell, rng.random(n) + 0.1
+    pb = PBCCalculator(cell)
+    mine = pts.copy()
+    pb.wrap_points(mine)
+    np.testing.assert_allclose(mine, oracle.wrap_points(cell, pts), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(pb.distances(pt1, pts), oracle.distances(cell, pt1, pts), rtol=1e-12)
+    np.testing.assert_allclose(pb.average(pts), oracle.average(cell, pts), rtol=0, atol=1e-10)
+    np.testing.assert_allclose(pb.average(pts, w), oracle.average(cell, pts, w), rtol=0, atol=1e-10)
+
+
+def test_site_vertex_distances_of_a_few_sites():
+    """D = 3 sites of up to V = 3 vertices among S = 5 static atoms (every table of the call ends off a 16-byte boundary),
+    against the CPU oracle; a padded vertex gives NaN."""
+    from oracle import oracle
+    from sitator_amd import _lib
+    cell = G.load("pbc_known_answers")["tri/cell"]
+    rng = np.random.default_rng(75)
+    centers, ref_static = rng.random((3, 3)) @ cell, rng.random((5, 3)) @ cell
+    verts = np.array([[0, 1, 2], [4, 3, -1], [2, -1, -1]], dtype=np.int64)
+    ctx = _lib.HipContext(cell)
+    got = ctx.site_vertex_distances(centers, ref_static, verts)
+    ctx.close()
+    exp = np.full(verts.shape, np.nan)
+    for k, row in enumerate(verts):
+        exp[k, :np.sum(row >= 0)] = oracle.distances(cell, centers[k], ref_static[row[row >= 0]])
+    assert np.array_equal(np.isnan(got), verts < 0)
+    np.testing.assert_allclose(got, exp, rtol=1e-12)

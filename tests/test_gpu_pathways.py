@@ -100,6 +100,16 @@ def test_min_image_on_the_connected_pairs(contexts, name):
     assert np.array_equal(moved, exp_moved) and np.array_equal(codes, exp_codes)
 
 
+@pytest.mark.parametrize("n", [1, 3, 5])
+def test_min_image_of_a_few_pairs(contexts, n):
+    """Counts at which every piece of the call's scratch layout ends off a 16-byte boundary."""
+    rng = np.random.default_rng(40 + n)
+    ref, pts = rng.random((n, 3)) @ PR.TRICLINIC, rng.random((n, 3)) @ PR.TRICLINIC
+    moved, codes = contexts(PR.TRICLINIC).min_image(ref, pts)
+    exp_moved, exp_codes = PR.min_image(PR.TRICLINIC, ref, pts)
+    assert np.array_equal(moved, exp_moved) and np.array_equal(codes, exp_codes)
+
+
 def test_pbc_calculator_min_image_in_place_and_ties(contexts):
     from sitator_amd import PBCCalculator
     pbcc = PBCCalculator(PR.CUBIC, _ctx=contexts(PR.CUBIC))
@@ -118,7 +128,8 @@ def test_pbc_calculator_min_image_in_place_and_ties(contexts):
 @pytest.mark.parametrize("K,cell,seed,kw", [
     (40, "cubic", 11, {}), (63, "triclinic", 12, {}), (64, "cubic", 13, {"connectivity_threshold": 2}),
     (65, "triclinic", 14, {"connectivity_threshold": 0.004}), (127, "cubic", 15, {}), (128, "triclinic", 16, {}),
-    (129, "cubic", 17, {"true_periodic_pathways": False, "minimum_n_sites": 3}), (130, "triclinic", 18, {})])
+    (129, "cubic", 17, {"true_periodic_pathways": False, "minimum_n_sites": 3}), (130, "triclinic", 18, {}),
+    (3, "triclinic", 19, {}), (3, "cubic", 20, {"true_periodic_pathways": False})])   # every scratch piece ends off a 16-byte boundary
 def test_fuzz_against_the_restatement(contexts, K, cell, seed, kw):
     cell = PR.CUBIC if cell == "cubic" else PR.TRICLINIC
     centers, n_ij = PR.random_network(cell, K, seed)

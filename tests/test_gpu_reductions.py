@@ -468,12 +468,44 @@ def test_best_match_on_random_rows_within_the_dot_product_bound():
         assert np.all(ld - ld[r] <= bound + bound[r]), what
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("runs", [None, "0"])
+@pytest.mark.parametrize("D", [5, 7])
+def test_reductions_and_matches_at_an_odd_landmark_dimension(D, runs, monkeypatch):
+    """F = 5, M = 3, K = 3, G = 3 and an odd D: every table of gram, weighted_row_sums, best_match and best_match_groups
+    ends off a 16-byte boundary in the scratch buffer.  Dyadic values, so the integer model, its rounded doubles and
+    numpy's argmax are the references, as above."""
+    F, M, K, G = 5, 3, 3, 3
+    rng = np.random.default_rng(900 + D)
+    X = np.where(rng.random((F * M, D)) < 0.6, rng.integers(1, 512, size=(F * M, D)) * rng.choice([-1.0, 1.0], size=(F * M, D)), 0.0) / 1024.0
+    lab = rng.integers(-1, K, size=(F, M))
+    confs = rng.integers(0, 65, size=(F, M)) / 64.0
+    cvec = rng.integers(1, 512, size=D) * rng.choice([-1.0, 1.0], size=D) / 1024.0
+    grp = (np.arange(D) % G).astype(np.int32)
+    _set_runs(monkeypatch, runs)
+    c = _rows_ctx(X, lab, confs)
+    ghi, glo, gseen = R.gram_reference(X)
+    hi, lo, seen = c.gram_limbs()
+    assert np.array_equal(seen, gseen) and np.array_equal(hi, ghi) and np.array_equal(lo, glo)
+    Gm, seen = c.gram()
+    assert np.array_equal(seen, gseen) and R.ulp_distance(Gm, R.rounded_values(ghi, glo)) <= 1.0
+    for weighted in (True, False):
+        rhi, rlo = R.row_sums_reference(X, lab, confs, K, weighted)
+        hi, lo = c.weighted_row_sums_limbs(K, weighted=weighted)
+        assert np.array_equal(hi, rhi) and np.array_equal(lo, rlo), weighted
+        sums, wsum = c.weighted_row_sums(K, weighted=weighted)
+        assert R.ulp_distance(np.concatenate([sums.reshape(-1), wsum]), R.rounded_values(rhi, rlo)) <= 1.0, weighted
+    _same_match(c.best_match(cvec), R.sparse_products_argmax(X, cvec), "D=%d" % D)
+    _same_groups(c.best_match_groups(grp, cvec, G), _group_reference(X, grp, cvec, G), "D=%d" % D)
+
+
 # ---- site anchors and sums ------------------------------------------------------------------------------------------------
 
 # (host, M, F, K): N in {1, 255, 16384, 16385, 3 * 16384 + 5, 4095, 4097}, K in {1, 480, 8192, 8193, 4266}; an orthorhombic,
 # a triclinic and a hexagonal cell
 SITE_CASES = [("C1", 1, 1, 1), ("C1b", 3, 85, 480), ("C2", 64, 256, 480), ("C1b", 1, 16385, 8192), ("C1", 1, 49157, 8193),
-              ("C1b", 63, 65, 300), ("C2h", 17, 241, 40), ("C2", 64, 300, 4266)]
+              ("C1b", 63, 65, 300), ("C2h", 17, 241, 40), ("C2", 64, 300, 4266),
+              ("C1b", 3, 5, 3), ("C1", 3, 5, 5)]         # the last two: every table of the two calls ends off a 16-byte boundary
 SITE_K_LIMIT = 4266                         # sit_site_sums: K * 36 bytes of LDS within 150 KiB
 
 

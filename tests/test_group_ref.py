@@ -139,7 +139,17 @@ int main(int argc, char **argv)
 {
     if (argc != 4) return 2;
     const int64_t n = atoll(argv[1]), K = atoll(argv[2]), M = atoll(argv[3]);
-    const GroupPlan p = gp_plan(n, K, M);
+    GroupPlan p = gp_plan(n, K, M);
+    // the scratch layout: sized on a null base, then carved over a heap buffer of exactly that size
+    Carve size = {nullptr, 0};
+    p.lay(size);
+    char *base = (char *)malloc((size_t)size.used);
+    Carve cv = {base, 0};
+    p.lay(cv);
+    if (cv.used != size.used) return 3;
+    const long long o_status = (char *)p.status - base, o_totals = (char *)p.totals - base, o_offsets = (char *)p.offsets - base,
+                    o_midx = (char *)p.midx - base, o_table = (char *)p.table - base, scratch_bytes = cv.used;
+    free(base);
     long long covered = 1;
     if (p.ok && n <= ((int64_t)1 << 24)) {
         std::vector<unsigned char> seen((size_t)n, 0);
@@ -154,8 +164,7 @@ int main(int argc, char **argv)
         for (int64_t i = 0; i < n; i++) if (seen[(size_t)i] != 1) covered = 0;
     }
     printf("%d %lld %d %d %lld %lld %lld %lld %lld %lld %lld %lld %d %d %d %lld %lld %lld\n", p.ok, (long long)p.n_chunks, p.lds, p.label_bits,
-           (long long)p.table_words, (long long)p.o_status, (long long)p.o_totals, (long long)p.o_offsets, (long long)p.o_midx,
-           (long long)p.o_table, (long long)p.scratch_bytes, covered, GP_CHUNK, GP_TILE, GP_LDS_MAX_SITES,
+           (long long)p.table_words, o_status, o_totals, o_offsets, o_midx, o_table, scratch_bytes, covered, GP_CHUNK, GP_TILE, GP_LDS_MAX_SITES,
            (long long)gp_frames_per_stage(0, 1000, 10), (long long)gp_frames_per_stage(240, 1000, 10),
            (long long)gp_frames_per_stage(239, 1000, 10));
     return 0;

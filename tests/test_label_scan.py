@@ -1,6 +1,6 @@
 """CPU-only: the chunk algebra of the label scans (sitator_amd/csrc/label_scan.h: jump detection, JumpAnalysis,
-assign_to_last_known_site, ReplaceUnassignedPositions) and the scratch carver, compiled with the host compiler under
-ASan / UBSan the way test_fill3_plan.py compiles the launch planner.  The probe runs what the kernels of dynamics.hip
+assign_to_last_known_site, ReplaceUnassignedPositions) and their scratch layouts, compiled with the host compiler under
+ASan / UBSan the way test_fill3_plan.py compiles the launch planner (the carver itself: test_scratch_carve.py).  The probe runs what the kernels of dynamics.hip
 run - ls_summarise per (chunk, ion), the *_advance chain per ion, the *_step replay per (chunk, ion) - at ANY chunk
 length, through pointers a Carve handed out over a heap buffer of exactly the size the same layout asked for, and next
 to it a serial fold of the *_step functions from frame 0 (for the backward chain: from the last frame)."""
@@ -50,19 +50,8 @@ template <class S> static void inside(const ScanScratch<S> &s, i64 M, i64 nch)
 }
 static void put(const void *p, i64 n) { fwrite(p, 8, (size_t)n, stdout); }
 
-static void carver_self_test()
-{
-    i64 *a; i32 *b; char *c; double *d;
-    carve([&](Carve &cv) { a = cv.take<i64>(3); b = cv.take<i32>(0); c = cv.take<char>(1); d = cv.take<double>(2); });
-    inside(a, 3); inside(b, 0); inside(c, 1); inside(d, 2);
-    if (g_used != 64 || (char *)b != (char *)c || (char *)a + 32 != c || c + 16 != (char *)d) { fprintf(stderr, "carver\n"); exit(3); }
-    a[0] = a[2] = 1; c[0] = 2; d[0] = d[1] = 3.0;       // n = 0 took no bytes: nothing is written through b
-    free(g_base);
-}
-
 int main()
 {
-    carver_self_test();
     i64 h[5];
     if (fread(h, 8, 5, stdin) != 5) return 2;
     const i64 F = h[0], M = h[1], chunk = h[2], halo = h[3], threshold = h[4], nch = ls_chunks(F, chunk);
