@@ -70,7 +70,7 @@ const char *sit_last_message(sit_ctx *ctx);
  * frame), out[5] = bytes of a communicator id (sit_comm_unique_id).  Writes min(n, 6) words and returns 6.  A binding
  * checks its own struct declarations against these once, at import (tests/test_abi.py does it for the ctypes stubs of
  * INTEGRATION.md and sitator_amd/_lib.py).  No context, no GPU needed.                                        */
-#define SIT_ABI_VERSION 10
+#define SIT_ABI_VERSION 11
 int sit_abi(int32_t *out, int n);
 /* Device buffers of 1 MB and more (the trajectory, the landmark rows, labels, the fit's arena) are kept by the process
  * when a context lets go of them, up to as much as its contexts have held at once, and handed to the next context that asks for a similar size: a process
@@ -474,6 +474,32 @@ int sit_barrier_energies(sit_ctx *ctx, const double *static_pos, const double *e
  * into the cell (floor(rc / h_a) + 1, h_a the perpendicular height), static atoms per LDS tile, threads per workgroup, LDS
  * bytes per workgroup}.  SIT_ERR_INVALID: a degenerate cell, rc not positive or beyond 255 heights.                        */
 int sit_barrier_plan(const double *cell, double rc, int64_t *out6);
+
+/* ---- Voronoi nodes of the static lattice (voronoi.py, which asks the Zeo++ `network` binary) --------------------------------- */
+
+/* The periodic Voronoi nodes of static_pos[S, 3] (any periodic image) under the context's cell, for a tolerance tau in Angstrom
+ * (csrc/voronoi_plan.h).  A node is a sphere (c, r) with no atom image closer to c than r - tau and at least four atom images,
+ * not coplanar, within [r - tau, r + tau]; its vertices are the static indices of all atom images in that shell, unique and
+ * ascending - one degenerate sphere is one node with all of its atoms, and in a cell so small that images of one atom share a
+ * sphere a node has fewer than 4 vertices.  Two-call convention: every call sets *n_nodes and *n_indices (the sizes needed),
+ * status[S] (0 done, 1 the search radius would have to grow further, 2 an uncertain test was met, 3 a capacity of
+ * sit_voronoi_plan was exceeded), nbr_count[S] (atom images within the atom's last search radius) and info8 = {rounds of the
+ * search radius, the last radius, the largest neighbour count, records before the merge, kernel milliseconds (HIP events), the
+ * first radius, the status of the merge (2: two record centres between 16 tau and 64 tau apart), 0}; when n_nodes <= node_cap
+ * and n_indices <= index_cap it also fills centers[n_nodes, 3] (wrapped into the cell), radii[n_nodes], offsets[n_nodes + 1] and
+ * indices[n_indices] (CSR of the vertices).  The result of the last call is kept with the context: the fill call after a size
+ * call with the same input computes nothing.  Unless every status is 0 and the merge is unambiguous there are no nodes
+ * (n_nodes = 0): a partial network is never returned.  Nodes come in the order of their first record (atoms ascending, the
+ * enumeration of voronoi_plan.h inside an atom); nothing depends on arrival: the same bytes on every call.  status, nbr_count,
+ * info8 and the four result arrays are optional.  SIT_ERR_INVALID: a missing array, S < 1, tau not positive, a degenerate cell, a
+ * position that is not finite or more than 2^20 cells from the origin.  Reads nothing of the context but its cell.            */
+int sit_voronoi_nodes(sit_ctx *ctx, const double *static_pos, int64_t S, double tau, int64_t node_cap, int64_t index_cap,
+                      int64_t *n_nodes, int64_t *n_indices, double *centers, double *radii, int64_t *offsets, int32_t *indices,
+                      int32_t *status, int32_t *nbr_count, double *info8);
+/* The plan of sit_voronoi_nodes for cell[9] (rows are the cell vectors) and S atoms, no context needed: out8 = {neighbour cap,
+ * record cap per atom, atom images per sphere, threads per workgroup, LDS bytes per workgroup, rounds at most, bytes of a
+ * record, 1 / VP_SHAPE_MIN}; radius2 (optional) = {the first search radius, the growth factor}.                             */
+int sit_voronoi_plan(const double *cell, int64_t S, int64_t *out8, double *radius2);
 
 /* ---- frame sharding across GPUs ------------------------------------ */
 

@@ -7,7 +7,7 @@ Host code is Python and talks to hand-written HIP kernels (gfx950) through the c
     st = LandmarkAnalysis(clustering_algorithm="dotprod").run(sn, frames)
 """
 from .errors import (InsufficientSitesError, LandmarkAnalysisError, MultipleOccupancyError,  # noqa: F401
-                     StaticLatticeError, ZeroLandmarkError)
+                     StaticLatticeError, VoronoiError, ZeroLandmarkError)
 from .site_network import SiteNetwork, Structure  # noqa: F401
 from .site_trajectory import SiteGrouping, SiteTrajectory  # noqa: F401
 from .pbc import PBCCalculator  # noqa: F401
@@ -19,6 +19,7 @@ from .merging import MergeSites, MergeSitesError, MergedSitesTooDistantError  # 
 from .recenter import RecenterTrajectory  # noqa: F401
 from .misc import NAvgsPerSite  # noqa: F401
 from .network import DiffusionPathwayAnalysis, MergeSitesByBarrier  # noqa: F401
+from .voronoi import VoronoiSiteGenerator  # noqa: F401
 from . import calculators  # noqa: F401
 from .site_descriptors import InsufficientCoordinatingAtomsError, SiteVolumes  # noqa: F401
 

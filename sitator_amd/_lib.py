@@ -40,7 +40,7 @@ class FillParams(C.Structure):
                    int(store_rows), int(assign), int(predict_normed), int(defer), float(predict_threshold))
 
 
-ABI_VERSION = 10         # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
+ABI_VERSION = 11         # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
 
 
 # every symbol include/sitator_hip.h declares: (restype, argtypes)
@@ -116,6 +116,8 @@ SIGNATURES = {
     "sit_barrier_energies": (C.c_int, [_vp, _dp, _dp, _dp, i64, C.c_double, _dp, i64, _i32p, i64, _dp, i64, C.c_double, _dp, _u8p,
                                        _i32p]),
     "sit_barrier_plan": (C.c_int, [_dp, C.c_double, _ip]),
+    "sit_voronoi_nodes": (C.c_int, [_vp, _dp, i64, C.c_double, i64, i64, _ip, _ip, _dp, _dp, _ip, _i32p, _i32p, _i32p, _dp]),
+    "sit_voronoi_plan": (C.c_int, [_dp, i64, _ip, _dp]),
     "sit_comm_unique_id": (C.c_int, [_u8p]),
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
     "sit_comm_destroy": (C.c_int, [_vp]),
@@ -197,6 +199,19 @@ def barrier_plan(cell, rc):
     if load().sit_barrier_plan(_d(cell), float(rc), _i(out)) != OK:
         raise ValueError("barrier_plan: a degenerate cell, or rc not positive or beyond 255 perpendicular heights of the cell")
     return {"translations": tuple(int(v) for v in out[:3]), "tile": int(out[3]), "threads": int(out[4]), "lds_bytes": int(out[5])}
+
+
+def voronoi_plan(cell, S):
+    """The plan of ``voronoi_nodes`` for ``cell`` (rows are the cell vectors) and ``S`` atoms (``sit_voronoi_plan``): the caps, the
+    workgroup, and the first search radius with its growth factor."""
+    out, rad = np.zeros(8, dtype=np.int64), np.zeros(2)
+    cell = _f64(cell).reshape(3, 3)
+    if load().sit_voronoi_plan(_d(cell), int(S), _i(out), _d(rad)) != OK:
+        raise ValueError("voronoi_plan: a degenerate cell or no atom")
+    keys = ["neighbour_cap", "record_cap", "member_cap", "threads", "lds_bytes", "max_rounds", "record_bytes", "inverse_shape_min"]
+    plan = {k: int(v) for k, v in zip(keys, out)}
+    plan["first_radius"], plan["growth"] = float(rad[0]), float(rad[1])
+    return plan
 
 
 def release_cached_memory():
@@ -935,6 +950,30 @@ class HipContext(object):
             verdict.ctypes.data_as(_u8p), None if code is None else code.ctypes.data_as(_i32p)))
         return en, verdict, code
 
+    # -- VoronoiSiteGenerator: reads nothing of the context but its cell
+    def voronoi_nodes(self, static_pos, tau):
+        """``{"centers" [n, 3], "radii" [n], "vertices" (list of n int arrays), "status" int32 [S], "nbr_count" int32 [S],
+        "info" dict}`` (``sit_voronoi_nodes``, size call then fill call): the periodic Voronoi nodes of ``static_pos`` ``[S, 3]``
+        under the context's cell for the tolerance ``tau``.  Unless every status is 0 and the merge unambiguous there are no nodes."""
+        static_pos = _f64(static_pos).reshape(-1, 3)
+        S = len(static_pos)
+        status, nbr = np.zeros(S, dtype=np.int32), np.zeros(S, dtype=np.int32)
+        info = np.zeros(8)
+        nn, ni = i64(0), i64(0)
+        head = (self._h, _d(static_pos), S, float(tau))
+        tail = (status.ctypes.data_as(_i32p), nbr.ctypes.data_as(_i32p), _d(info))
+        self._check(self.lib.sit_voronoi_nodes(*head, 0, 0, C.byref(nn), C.byref(ni), None, None, None, None, *tail))
+        n, m = int(nn.value), int(ni.value)
+        centers, radii = np.zeros((n, 3)), np.zeros(n)
+        offsets, indices = np.zeros(n + 1, dtype=np.int64), np.zeros(max(m, 1), dtype=np.int32)
+        self._check(self.lib.sit_voronoi_nodes(*head, n, m, C.byref(nn), C.byref(ni), _d(centers), _d(radii), _i(offsets),
+                                               indices.ctypes.data_as(_i32p), *tail))
+        assert int(nn.value) == n and int(ni.value) == m
+        keys = ["rounds", "final_radius", "max_neighbours", "records", "kernel_ms", "first_radius", "merge_status"]
+        out_info = {k: (float(v) if k in ("final_radius", "kernel_ms", "first_radius") else int(v)) for k, v in zip(keys, info)}
+        return {"centers": centers, "radii": radii, "vertices": [indices[offsets[j]:offsets[j + 1]].copy() for j in range(n)],
+                "status": status, "nbr_count": nbr, "info": out_info}
+
     # ---- RCCL exchange of the frame-sharded path (csrc/comm.hip) ----
     def comm_create(self, unique_id, rank, world):
         uid = np.frombuffer(bytes(unique_id), dtype=np.uint8).copy()
@@ -1059,6 +1098,6 @@ for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "a
               "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
               "unknown_runs", "replace_closer", "clamp_trajectory", "group_by_site", "grouped_fetch", "grouped_bucket_averages",
               "grouped_recenter_step", "grouped_hull_volumes", "grouped_work_fetch", "min_image", "pathway_components",
-              "barrier_energies"):
+              "barrier_energies", "voronoi_nodes"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

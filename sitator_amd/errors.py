@@ -77,6 +77,28 @@ class UnassignedClampError(RuntimeError):
         self.first_unassigned = first_unassigned
 
 
+class VoronoiError(Exception):
+    """``VoronoiSiteGenerator``: the Voronoi cell of some static atoms could not be certified, or the records could not be
+    clustered into nodes unambiguously.  Attributes: ``atoms`` (static indices), ``statuses`` (per atom: 1 the search radius
+    would have to grow beyond the plan, 2 a test within its error bound of a threshold, 3 a capacity of the plan exceeded),
+    ``ambiguous`` (two sphere centres between 16 and 64 tolerances apart)."""
+
+    NAMES = {1: "search radius beyond the plan", 2: "uncertain", 3: "capacity exceeded"}
+
+    def __init__(self, atoms, statuses, ambiguous=False):
+        self.atoms = [int(a) for a in atoms]
+        self.statuses = [int(s) for s in statuses]
+        self.ambiguous = bool(ambiguous)
+        if ambiguous:
+            text = "Voronoi nodes: two sphere centres lie between 16 and 64 tolerances apart; the clustering into nodes is ambiguous."
+        else:
+            kinds = sorted(set(self.statuses))
+            text = "Voronoi nodes: %d static atoms could not be certified: %s." % (
+                len(self.atoms), "; ".join("%s: atoms %s" % (self.NAMES.get(k, "status %d" % k),
+                                                              [a for a, s in zip(self.atoms, self.statuses) if s == k][:16]) for k in kinds))
+        super(VoronoiError, self).__init__(text)
+
+
 class DeviceDomainError(Exception):
     """Internal: a domain error reported by the C-ABI before it is mapped to the classes above."""
 
