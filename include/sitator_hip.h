@@ -70,7 +70,7 @@ const char *sit_last_message(sit_ctx *ctx);
  * frame), out[5] = bytes of a communicator id (sit_comm_unique_id).  Writes min(n, 6) words and returns 6.  A binding
  * checks its own struct declarations against these once, at import (tests/test_abi.py does it for the ctypes stubs of
  * INTEGRATION.md and sitator_amd/_lib.py).  No context, no GPU needed.                                        */
-#define SIT_ABI_VERSION 11
+#define SIT_ABI_VERSION 12
 int sit_abi(int32_t *out, int n);
 /* Device buffers of 1 MB and more (the trajectory, the landmark rows, labels, the fit's arena) are kept by the process
  * when a context lets go of them, up to as much as its contexts have held at once, and handed to the next context that asks for a similar size: a process
@@ -500,6 +500,54 @@ int sit_voronoi_nodes(sit_ctx *ctx, const double *static_pos, int64_t S, double 
  * record cap per atom, atom images per sphere, threads per workgroup, LDS bytes per workgroup, rounds at most, bytes of a
  * record, 1 / VP_SHAPE_MIN}; radius2 (optional) = {the first search radius, the growth factor}.                             */
 int sit_voronoi_plan(const double *cell, int64_t S, int64_t *out8, double *radius2);
+
+/* ---- SOAP site descriptors (site_descriptors/SOAP.py, which asks QUIP or DScribe) --------------------------------------------- */
+
+/* The SOAP power spectrum of every centre of centers[P, 3] in the lattice static_pos[S, 3] under the context's cell
+ * (csrc/soap_plan.h; the GTO construction of Himanen et al. 2020 - agreement with a DScribe or QUIP
+ * installation is not claimed).  species_idx[S] (int32) is the index of an atom's species in the environment list, -1: not in the
+ * environment.  Per environment species Z the density is a Gaussian of width sigma on every periodic image of every atom of Z
+ * within cutoff of the centre (hard cut; with width = cutoff_transition_width > 0 weighted by 1 up to cutoff - width and
+ * 0.5 (1 + cos(pi (d - cutoff + width) / width)) beyond); it is expanded in g_nl(r) = sum_n' beta[l][n][n'] r^l exp(-alpha[l][n'] r^2)
+ * times real orthonormal spherical harmonics - alpha[(l_max + 1), n_max] and beta[(l_max + 1), n_max, n_max] are the caller's
+ * tables - and out[P, n_dim] holds p = pi sqrt(8 / (2 l + 1)) sum_m c_Z1,nlm c_Z2,n'lm: species pairs outermost in the order of the
+ * environment list (crossover: all Z1 <= Z2, else Z1 = Z2), then n, then n' (n' >= n when Z1 = Z2), then l.  n_dim must be the
+ * length sit_soap_plan reports.  nbr_count[P] (optional, int32): the images within the cutoff.  Complete for any cell shape,
+ * cells shorter than the cutoff and positions outside the cell; a centre on an atom is an ordinary input; every sum runs in a
+ * fixed order (no floating-point atomics): the same bytes on every call.  SIT_ERR_INVALID: a missing array, a species index
+ * >= n_species, a cutoff, sigma or exponent that is not positive, width outside [0, cutoff], a cutoff beyond 255 perpendicular
+ * heights of the cell, a position that is not finite or more than 2^20 cells from the origin; SIT_ERR_CAPACITY (the message names
+ * the limit): l_max > 8, n_max > 8, more than 4 species.  P = 0 is SIT_OK and touches nothing.  Reads nothing of the context but
+ * its cell: frames, rows, labels and their validity stay as they are.                                                          */
+int sit_soap_vectors(sit_ctx *ctx, const double *static_pos, const int32_t *species_idx, int64_t S, const double *centers, int64_t P,
+                     double cutoff, double width, double sigma, int64_t n_species, int64_t n_max, int64_t l_max, int crossover,
+                     const double *alpha, const double *beta, int64_t n_dim, double *out, int32_t *nbr_count);
+/* The plan of the SOAP entry points for cell[9] (rows are the cell vectors), no context needed: out12 = {the translations
+ * |t_a| <= out12[a] as in sit_barrier_plan, threads per workgroup, neighbours staged at once (longer lists are taken in rounds),
+ * LDS bytes per workgroup, the largest l_max, n_max and number of species, coefficients per environment, n_dim without and with
+ * crossover}.  SIT_ERR_INVALID: a degenerate cell, a cutoff not positive or beyond 255 heights; SIT_ERR_CAPACITY: beyond a limit
+ * (the first nine values are set).                                                                                              */
+int sit_soap_plan(const double *cell, double cutoff, int64_t n_species, int64_t n_max, int64_t l_max, int64_t *out12);
+/* SOAPDescriptorAverages (SOAP.py:248-320) on the resident labels [F, M]: one SOAP vector per assigned mobile ion per strided frame
+ * (frame % stepsize == 0), taken among the static atoms static_idx[S] (columns of the frame, with species_idx[S] as above) OF ITS
+ * OWN FRAME, multiplied by 1 / averagings[site] and added to its row.  positions: a host [F, A, 3] array, staged in chunks of
+ * strided frames within workspace_bytes (0: 1 GiB; a cap below one frame is SIT_ERR_INVALID), or NULL for the resident frames;
+ * mobile_idx[M] names the atoms of the label columns.  The bucket plan (csrc/soap_plan.h): counts[K] = strided frames in which a
+ * site holds at least one ion; of several ions on one site in one frame the last in ion order contributes; averaging is the
+ * argument, or floor(mean(counts) / avg_descriptors_per_site) with 0 made 1 (exactly one of the two is positive);
+ * nr_of_descs[K] = max(counts / averaging, 1), averagings = averaging, or counts where counts < averaging; the k-th frame of a
+ * site goes to row first_row + k / averagings while that is one of its rows; a site never visited keeps one zero row.  The
+ * vectors of a row are added in ascending frame order; nothing depends on arrival.  Every call sets *n_rows, counts and
+ * nr_of_descs; when descs is given and *n_rows <= row_cap it also fills descs[*n_rows, n_dim].  info4 (optional) = {kernel
+ * milliseconds (HIP events), contributing environments, chunks, the averaging used (0: it came out as 0 and 1 was taken)}.
+ * Labels are looked at before anything is indexed with them, as in sit_clamp_trajectory.  Errors as sit_soap_vectors.  Reads
+ * only: frames, rows, labels and their validity stay as they are.                                                            */
+int sit_soap_site_averages(sit_ctx *ctx, const double *positions, int64_t F, int64_t A, const int64_t *static_idx,
+                           const int32_t *species_idx, int64_t S, const int64_t *mobile_idx, int64_t M, int64_t K, int64_t stepsize,
+                           int64_t averaging, int64_t avg_descriptors_per_site, double cutoff, double width, double sigma,
+                           int64_t n_species, int64_t n_max, int64_t l_max, int crossover, const double *alpha, const double *beta,
+                           int64_t n_dim, int64_t workspace_bytes, int64_t row_cap, int64_t *n_rows, int64_t *counts,
+                           int64_t *nr_of_descs, double *descs, double *info4);
 
 /* ---- frame sharding across GPUs ------------------------------------ */
 

@@ -17,10 +17,11 @@ from .dynamics import (AverageVibrationalFrequency, GenerateClampedTrajectory, J
                        MergeSitesByThreshold, RemoveUnoccupiedSites, ReplaceUnassignedPositions, SmoothSiteTrajectory)
 from .merging import MergeSites, MergeSitesError, MergedSitesTooDistantError  # noqa: F401
 from .recenter import RecenterTrajectory  # noqa: F401
-from .misc import NAvgsPerSite  # noqa: F401
+from .misc import GenerateAroundSites, NAvgsPerSite  # noqa: F401
 from .network import DiffusionPathwayAnalysis, MergeSitesByBarrier  # noqa: F401
 from .voronoi import VoronoiSiteGenerator  # noqa: F401
 from . import calculators  # noqa: F401
-from .site_descriptors import InsufficientCoordinatingAtomsError, SiteVolumes  # noqa: F401
+from .site_descriptors import (InsufficientCoordinatingAtomsError, SiteVolumes, SOAP, SOAPCenters,  # noqa: F401
+                               SOAPDescriptorAverages, SOAPSampledCenters, device_soap_backend)
 
 __version__ = "0.1.0"

@@ -40,7 +40,7 @@ class FillParams(C.Structure):
                    int(store_rows), int(assign), int(predict_normed), int(defer), float(predict_threshold))
 
 
-ABI_VERSION = 11         # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
+ABI_VERSION = 12         # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
 
 
 # every symbol include/sitator_hip.h declares: (restype, argtypes)
@@ -118,6 +118,11 @@ SIGNATURES = {
     "sit_barrier_plan": (C.c_int, [_dp, C.c_double, _ip]),
     "sit_voronoi_nodes": (C.c_int, [_vp, _dp, i64, C.c_double, i64, i64, _ip, _ip, _dp, _dp, _ip, _i32p, _i32p, _i32p, _dp]),
     "sit_voronoi_plan": (C.c_int, [_dp, i64, _ip, _dp]),
+    "sit_soap_vectors": (C.c_int, [_vp, _dp, _i32p, i64, _dp, i64, C.c_double, C.c_double, C.c_double, i64, i64, i64, C.c_int, _dp, _dp,
+                                   i64, _dp, _i32p]),
+    "sit_soap_plan": (C.c_int, [_dp, C.c_double, i64, i64, i64, _ip]),
+    "sit_soap_site_averages": (C.c_int, [_vp, _dp, i64, i64, _ip, _i32p, i64, _ip, i64, i64, i64, i64, i64, C.c_double, C.c_double,
+                                         C.c_double, i64, i64, i64, C.c_int, _dp, _dp, i64, i64, i64, _ip, _ip, _ip, _dp, _dp]),
     "sit_comm_unique_id": (C.c_int, [_u8p]),
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
     "sit_comm_destroy": (C.c_int, [_vp]),
@@ -199,6 +204,24 @@ def barrier_plan(cell, rc):
     if load().sit_barrier_plan(_d(cell), float(rc), _i(out)) != OK:
         raise ValueError("barrier_plan: a degenerate cell, or rc not positive or beyond 255 perpendicular heights of the cell")
     return {"translations": tuple(int(v) for v in out[:3]), "tile": int(out[3]), "threads": int(out[4]), "lds_bytes": int(out[5])}
+
+
+def soap_plan(cell, cutoff, n_species, n_max, l_max):
+    """The plan of ``soap_vectors`` / ``soap_site_averages`` for ``cell`` (rows are the cell vectors) (``sit_soap_plan``): the
+    translations, the workgroup, the neighbours staged at once, the LDS bytes, the limits and the lengths of a vector.  Beyond a
+    limit: ``RuntimeError``."""
+    out = np.zeros(12, dtype=np.int64)
+    cell = _f64(cell).reshape(3, 3)
+    rc = load().sit_soap_plan(_d(cell), float(cutoff), int(n_species), int(n_max), int(l_max), _i(out))
+    limits = {"max_l": int(out[6]), "max_n": int(out[7]), "max_species": int(out[8])}
+    if rc == E_CAPACITY:
+        raise RuntimeError("soap_plan: l_max, n_max or the number of environment species is beyond %r" % limits)
+    if rc != OK:
+        raise ValueError("soap_plan: a degenerate cell, or a cutoff not positive or beyond 255 perpendicular heights of the cell")
+    plan = {"translations": tuple(int(v) for v in out[:3]), "threads": int(out[3]), "nbr_cap": int(out[4]), "lds_bytes": int(out[5]),
+            "n_coef": int(out[9]), "n_dim": int(out[10]), "n_dim_crossover": int(out[11])}
+    plan.update(limits)
+    return plan
 
 
 def voronoi_plan(cell, S):
@@ -974,6 +997,64 @@ class HipContext(object):
         return {"centers": centers, "radii": radii, "vertices": [indices[offsets[j]:offsets[j + 1]].copy() for j in range(n)],
                 "status": status, "nbr_count": nbr, "info": out_info}
 
+    # -- SOAP descriptors: soap_vectors reads nothing of the context but its cell, soap_site_averages labels and frames only
+    def _soap_args(self, soap):
+        """The tail of scalars and tables the SOAP entry points share, from a ``soap`` dict (``site_descriptors.soap_tables``), and
+        the arrays its pointers point into (the caller holds them for the duration of the call)."""
+        alpha, beta = _f64(soap["alpha"]), _f64(soap["beta"])
+        L, n = int(soap["l_max"]) + 1, int(soap["n_max"])
+        assert alpha.shape == (L, n) and beta.shape == (L, n, n)
+        return (float(soap["cutoff"]), float(soap["cutoff_transition_width"]), float(soap["atom_sigma"]), int(soap["n_species"]), n,
+                L - 1, int(bool(soap["crossover"])), _d(alpha), _d(beta), int(soap["n_dim"])), (alpha, beta)
+
+    def soap_vectors(self, static_pos, species_idx, centers, soap, nbr_count=False):
+        """``(out [P, n_dim], nbr_count int32 [P] or None)`` (``sit_soap_vectors``): the SOAP power spectrum of every centre among
+        the atoms ``static_pos`` ``[S, 3]`` and all their periodic images under the context's cell; ``species_idx`` ``[S]``: the
+        index of an atom's species in the environment list, -1 for an atom outside it.  ``soap``: the dict of
+        ``site_descriptors.soap_tables``.  Beyond a capacity ``RuntimeError``, anything else that does not fit ``ValueError``."""
+        static_pos = _f64(static_pos).reshape(-1, 3)
+        species_idx = np.ascontiguousarray(species_idx, dtype=np.int32).reshape(-1)
+        assert len(species_idx) == len(static_pos)
+        centers = _f64(centers).reshape(-1, 3)
+        tail, keep = self._soap_args(soap)
+        P = len(centers)
+        out = np.zeros((P, int(soap["n_dim"])))
+        cnt = np.zeros(P, dtype=np.int32) if nbr_count else None
+        self._check(self.lib.sit_soap_vectors(self._h, _d(static_pos), species_idx.ctypes.data_as(_i32p), len(static_pos), _d(centers), P,
+                                              *tail, _d(out), None if cnt is None else cnt.ctypes.data_as(_i32p)))
+        return out, cnt
+
+    def soap_site_averages(self, K, static_idx, species_idx, mobile_idx, soap, stepsize=1, averaging=None, avg_descriptors_per_site=None,
+                           positions=None, workspace_bytes=0):
+        """``(descs [R, n_dim], counts [K], nr_of_descs [K], info)`` (``sit_soap_site_averages``, size call then fill call): the
+        averaged SOAP vectors of ``SOAPDescriptorAverages`` on the resident labels; ``positions``: a host ``[F, A, 3]`` float64
+        array, without it the frames resident after ``set_frames`` are read.  A label ``>= K`` raises ``IndexError``."""
+        static_idx, mobile_idx = _i64(static_idx).reshape(-1), _i64(mobile_idx).reshape(-1)
+        species_idx = np.ascontiguousarray(species_idx, dtype=np.int32).reshape(-1)
+        assert len(species_idx) == len(static_idx)
+        if positions is not None:
+            positions = _f64(positions)
+            assert positions.ndim == 3 and positions.shape[2] == 3
+            F, A = positions.shape[0], positions.shape[1]
+        else:
+            F, A = self.F, self.A
+        K = int(K)
+        tail, keep = self._soap_args(soap)
+        counts, nr = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
+        info = np.zeros(4)
+        n_rows = i64(0)
+        head = (self._h, None if positions is None else _d(positions), int(F), int(A), _i(static_idx), species_idx.ctypes.data_as(_i32p),
+                len(static_idx), _i(mobile_idx), len(mobile_idx), K, int(stepsize), int(averaging or 0), int(avg_descriptors_per_site or 0))
+        self._check_index(self.lib.sit_soap_site_averages(*head, *tail, int(workspace_bytes), 0, C.byref(n_rows), _i(counts), _i(nr),
+                                                          None, _d(info)))
+        R = int(n_rows.value)
+        descs = np.zeros((R, int(soap["n_dim"])))
+        self._check_index(self.lib.sit_soap_site_averages(*head, *tail, int(workspace_bytes), R, C.byref(n_rows), _i(counts), _i(nr),
+                                                          _d(descs), _d(info)))
+        assert int(n_rows.value) == R
+        return descs, counts, nr, {"kernel_ms": float(info[0]), "contributors": int(info[1]), "chunks": int(info[2]),
+                                   "averaging": int(info[3])}
+
     # ---- RCCL exchange of the frame-sharded path (csrc/comm.hip) ----
     def comm_create(self, unique_id, rank, world):
         uid = np.frombuffer(bytes(unique_id), dtype=np.uint8).copy()
@@ -1098,6 +1179,6 @@ for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "a
               "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
               "unknown_runs", "replace_closer", "clamp_trajectory", "group_by_site", "grouped_fetch", "grouped_bucket_averages",
               "grouped_recenter_step", "grouped_hull_volumes", "grouped_work_fetch", "min_image", "pathway_components",
-              "barrier_energies", "voronoi_nodes"):
+              "barrier_energies", "voronoi_nodes", "soap_vectors", "soap_site_averages"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

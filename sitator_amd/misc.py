@@ -1,7 +1,8 @@
-"""``NAvgsPerSite`` (reference: ``sitator/misc/NAvgsPerSite.py``) on the device-side grouping of the real positions by site
+"""``GenerateAroundSites`` (reference: ``sitator/misc/GenerateAroundSites.py``) and ``NAvgsPerSite`` (reference: ``sitator/misc/NAvgsPerSite.py``) on the device-side grouping of the real positions by site
 (``SiteTrajectory.group_real_positions``)."""
 import numpy as np
 
+from .site_network import SiteNetwork
 from .site_trajectory import SiteTrajectory
 
 
@@ -79,3 +80,30 @@ class NAvgsPerSite(object):
         sn.site_types = types
         assert not np.isnan(np.sum(sn.centers))
         return sn
+
+
+class GenerateAroundSites(object):
+    """``n`` normally distributed points (standard deviation ``sigma``) around every site: the sampling transform
+    ``SOAPSampledCenters`` names for a ``SiteNetwork``.  The ``site_types`` of the output are the index of the site a point was
+    generated from.  The numbers are drawn from ``np.random`` exactly as the reference draws them, so the same seed gives the same
+    centres; they are wrapped into the cell with ``PBCCalculator.wrap_points``."""
+
+    def __init__(self, n, sigma):
+        self.n = n
+        self.sigma = sigma
+
+    def run(self, sn):
+        from .pbc import PBCCalculator
+        assert isinstance(sn, SiteNetwork)
+        out = sn.copy()
+        pbcc = PBCCalculator(sn.structure.cell)
+        try:
+            newcenters = np.asarray(sn.centers).repeat(self.n, axis=0)
+            assert len(newcenters) == self.n * sn.n_sites
+            newcenters += self.sigma * np.random.standard_normal(size=newcenters.shape)
+            pbcc.wrap_points(newcenters)
+        finally:
+            pbcc._ctx.close()
+        out.centers = newcenters
+        out.site_types = np.repeat(np.arange(sn.n_sites), self.n)
+        return out

@@ -1,4 +1,10 @@
-"""``SiteVolumes`` (reference: ``sitator/site_descriptors/SiteVolumes.py``): the recentring of every site's point cloud runs on
+"""Site descriptors.
+
+``SOAP``, ``SOAPCenters``, ``SOAPSampledCenters``, ``SOAPDescriptorAverages`` (reference: ``sitator/site_descriptors/SOAP.py``) with
+``device_soap_backend``: the power spectrum of DESIGN.md section 17, evaluated on the GPU (``sit_soap_vectors``,
+``sit_soap_site_averages``).  The reference's QUIP and DScribe backends are not carried and there is no host fallback.
+
+``SiteVolumes`` (reference: ``sitator/site_descriptors/SiteVolumes.py``): the recentring of every site's point cloud runs on
 the GPU for all sites at once (``sit_grouped_recenter_step``); the convex hulls are qhull's on the host (``hulls="host"``, the
 default) or the device's (``hulls="device"``: ``sit_grouped_hull_volumes``, with qhull for the sites it flags)."""
 import logging
@@ -6,8 +12,9 @@ import time
 
 import numpy as np
 
+from . import _lib
 from .misc import resident_trajectory
-from .site_network import SiteNetwork
+from .site_network import SiteNetwork, Structure
 from .site_trajectory import SiteTrajectory
 
 logger = logging.getLogger(__name__)
@@ -170,3 +177,274 @@ class SiteVolumes(object):
     def run(self, st):
         """For backwards compatibility."""
         self.compute_accessable_volumes(st)
+
+
+# ---- SOAP --------------------------------------------------------------------------------------------------------------------
+
+CHEMICAL_SYMBOLS = (
+    "H He Li Be B C N O F Ne Na Mg Al Si P S Cl Ar K Ca Sc Ti V Cr Mn Fe Co Ni Cu Zn Ga Ge As Se Br Kr Rb Sr Y Zr Nb Mo Tc Ru Rh Pd "
+    "Ag Cd In Sn Sb Te I Xe Cs Ba La Ce Pr Nd Pm Sm Eu Gd Tb Dy Ho Er Tm Yb Lu Hf Ta W Re Os Ir Pt Au Hg Tl Pb Bi Po At Rn Fr Ra "
+    "Ac Th Pa U Np Pu Am Cm Bk Cf Es Fm Md No Lr Rf Db Sg Bh Hs Mt Ds Rg Cn Nh Fl Mc Lv Ts Og").split()
+atomic_numbers = dict((sym, z + 1) for z, sym in enumerate(CHEMICAL_SYMBOLS))
+assert len(CHEMICAL_SYMBOLS) == 118
+
+SOAP_DEFAULTS = {"cutoff": 3.0, "l_max": 6, "n_max": 6, "atom_sigma": 0.4, "crossover": False, "cutoff_transition_width": 0.0}
+
+
+def soap_radial_tables(cutoff, n_max, l_max):
+    """``(alpha [l_max + 1, n_max], beta [l_max + 1, n_max, n_max])`` of the radial basis ``g_nl(r) = sum_n' beta[l][n][n'] r^l
+    exp(-alpha[l][n'] r^2)``: ``r_n = linspace(1, cutoff, n_max)``, ``alpha = -ln(1e-3 / r_n^l) / r_n^2``, ``beta[l]`` the symmetric
+    (Loewdin) inverse root of the overlap ``S = 0.5 Gamma(l + 3/2) (alpha_n + alpha_n')^-(l + 3/2)``."""
+    from math import gamma
+    rn = np.linspace(1.0, float(cutoff), int(n_max))
+    alpha = np.empty((l_max + 1, n_max))
+    beta = np.empty((l_max + 1, n_max, n_max))
+    for l in range(l_max + 1):
+        alpha[l] = -np.log(1e-3 / rn ** l) / rn ** 2
+        overlap = 0.5 * gamma(l + 1.5) * (alpha[l][:, None] + alpha[l][None, :]) ** -(l + 1.5)
+        w, v = np.linalg.eigh(overlap)
+        beta[l] = (v / np.sqrt(w)) @ v.T
+    return alpha, beta
+
+
+def soap_n_dim(n_species, n_max, l_max, crossover):
+    same, cross = n_max * (n_max + 1) // 2 * (l_max + 1), n_max * n_max * (l_max + 1)
+    return n_species * same + (n_species * (n_species - 1) // 2 * cross if crossover else 0)
+
+
+def soap_tables(n_species, soap_params={}):
+    """The dict ``HipContext.soap_vectors`` takes: the parameters (``SOAP_DEFAULTS`` updated with ``soap_params``), the radial
+    tables and ``n_dim``."""
+    unknown = set(soap_params) - set(SOAP_DEFAULTS)
+    if unknown:
+        raise ValueError("Unknown SOAP parameters %r; the device backend knows %r" % (sorted(unknown), sorted(SOAP_DEFAULTS)))
+    soap = dict(SOAP_DEFAULTS)
+    soap.update(soap_params)
+    soap["l_max"], soap["n_max"], soap["n_species"] = int(soap["l_max"]), int(soap["n_max"]), int(n_species)
+    if soap["n_max"] < 1 or soap["l_max"] < 0 or not soap["cutoff"] > 0:
+        raise ValueError("SOAP needs n_max >= 1, l_max >= 0 and a positive cutoff")
+    soap["alpha"], soap["beta"] = soap_radial_tables(soap["cutoff"], soap["n_max"], soap["l_max"])
+    soap["n_dim"] = soap_n_dim(soap["n_species"], soap["n_max"], soap["l_max"], bool(soap["crossover"]))
+    return soap
+
+
+class _DeviceSoaper(object):
+    """What ``device_soap_backend`` hands to the operators: ``soaper(structure, positions)`` -> SOAP vectors, with ``n_dim``."""
+
+    def __init__(self, sn, soap_mask, tracer_atomic_number, environment_list, soap_params):
+        self.environment_list = [int(z) for z in environment_list]
+        self.soap = soap_tables(len(self.environment_list), soap_params)
+        self.n_dim = self.soap["n_dim"]
+        self.cell = np.asarray(sn.structure.cell, dtype=np.float64)
+
+    def species_idx(self, numbers):
+        """The index of every atom's species in the environment list, -1 for an atom outside it."""
+        idx = np.full(len(numbers), -1, dtype=np.int32)
+        for k, z in enumerate(self.environment_list):
+            idx[np.asarray(numbers) == z] = k
+        return idx
+
+    def __call__(self, structure, positions, ctx=None):
+        own = ctx is None
+        if own:
+            ctx = _lib.HipContext(self.cell)
+        try:
+            out, _ = ctx.soap_vectors(structure.positions, self.species_idx(structure.get_atomic_numbers()), positions, self.soap)
+        finally:
+            if own:
+                ctx.close()
+        return out
+
+
+def device_soap_backend(soap_params={}):
+    """The backend of the SOAP operators: ``soap_params`` may set ``cutoff`` (3.0), ``l_max`` (6), ``n_max`` (6), ``atom_sigma``
+    (0.4), ``crossover`` (False) and ``cutoff_transition_width`` (0: the hard cut)."""
+    soap_params = dict(soap_params)
+    soap_tables(1, soap_params)                                      # unknown keys and bad values fail here
+
+    def backend(sn, soap_mask, tracer_atomic_number, environment_list):
+        return _DeviceSoaper(sn, soap_mask, tracer_atomic_number, environment_list, soap_params)
+    backend._device_soap_backend = True
+    return backend
+
+
+class SOAP(object):
+    """Abstract base class for computing SOAP vectors in a ``SiteNetwork`` (``SOAP.py:13-147``).
+
+    ``tracer_atomic_number``: the atomic number of the tracer (``None``: the first mobile atom's).  ``environment``: atomic
+    numbers or symbols of the species to consider (``None``: every species the mask holds).  ``soap_mask``: which atoms of the
+    structure form the host - a boolean mask, a tuple of symbols, or ``None`` for the static structure.  ``backend``: ``None`` or
+    a ``device_soap_backend(...)``; anything else is a ``TypeError`` - the QUIP and DScribe backends are not carried."""
+
+    def __init__(self, tracer_atomic_number, environment=None, soap_mask=None, backend=None):
+        self.tracer_atomic_number = tracer_atomic_number
+        self._soap_mask = soap_mask
+        if backend is None:
+            backend = device_soap_backend()
+        if not getattr(backend, "_device_soap_backend", False):
+            raise TypeError("`backend` must be a device_soap_backend(...): the QUIP and DScribe backends of the reference are not "
+                            "carried, and there is no host fallback")
+        self._backend = backend
+        if environment is not None:
+            if not isinstance(environment, (list, tuple)):
+                raise TypeError('environment has to be a list or tuple of species (atomic number'
+                                ' or symbol of the environment to consider')
+            environment_list = []
+            for e in environment:
+                if isinstance(e, int):
+                    assert 0 < e <= max(atomic_numbers.values())
+                    environment_list.append(e)
+                elif isinstance(e, str):
+                    try:
+                        environment_list.append(atomic_numbers[e])
+                    except KeyError:
+                        raise KeyError("You provided a string that is not a valid atomic symbol")
+                else:
+                    raise TypeError("Environment has to be a list of atomic numbers or atomic symbols")
+            self._environment = environment_list
+        else:
+            self._environment = None
+
+    def _prepare(self, stn):
+        if isinstance(stn, SiteTrajectory):
+            sn = stn.site_network
+        elif isinstance(stn, SiteNetwork):
+            sn = stn
+        else:
+            raise TypeError("`stn` must be SiteNetwork or SiteTrajectory")
+        structure, tracer_atomic_number, soap_mask = self._make_structure(sn)
+        if self._environment is not None:
+            environment_list = self._environment
+        else:
+            environment_list = np.unique(sn.structure.get_atomic_numbers()[soap_mask])
+        soaper = self._backend(sn, soap_mask, tracer_atomic_number, environment_list)
+        return structure, tracer_atomic_number, soap_mask, soaper
+
+    def get_descriptors(self, stn):
+        """``(descs, desc_to_site)``: the descriptor vectors and, of equal length, the site each belongs to."""
+        structure, tracer_atomic_number, soap_mask, soaper = self._prepare(stn)
+        return self._get_descriptors(stn, structure, tracer_atomic_number, soap_mask, soaper)
+
+    def _make_structure(self, sn):
+        numbers = np.asarray(sn.structure.get_atomic_numbers())
+        if self._soap_mask is None:
+            soap_mask = sn.static_mask
+        else:
+            if isinstance(self._soap_mask, tuple):
+                symbols = np.array([CHEMICAL_SYMBOLS[z - 1] if 0 < z <= 118 else "X" for z in numbers])
+                soap_mask = np.isin(symbols, self._soap_mask)
+            else:
+                soap_mask = np.asarray(self._soap_mask, dtype=bool)
+            assert not np.any(soap_mask & sn.mobile_mask), \
+                "Error for atoms %s; No atom can be both static and mobile" % np.where(soap_mask & sn.mobile_mask)[0]
+        assert np.any(soap_mask), "Given `soap_mask` excluded all host atoms."
+        structure = Structure(np.asarray(sn.structure.positions, dtype=np.float64)[soap_mask], sn.structure.cell, numbers[soap_mask])
+        if self._environment is not None:
+            assert np.any(np.isin(numbers[soap_mask], self._environment)), \
+                "Combination of given `soap_mask` with the given `environment` excludes all host atoms."
+        if self.tracer_atomic_number is None:
+            tracer_atomic_number = numbers[sn.mobile_mask][0]
+        else:
+            tracer_atomic_number = self.tracer_atomic_number
+        if np.any(structure.get_atomic_numbers() == tracer_atomic_number):
+            raise ValueError("Structure cannot have static atoms (that are enabled in the SOAP mask) of the same species as "
+                             "`tracer_atomic_number`.")
+        return structure, tracer_atomic_number, soap_mask
+
+    def _get_descriptors(self, stn, structure, tracer_atomic_number, soap_mask, soaper):
+        raise NotImplementedError
+
+
+class SOAPCenters(SOAP):
+    """The SOAPs of the site centres in the fixed host structure (``SOAP.py:152-166``)."""
+
+    def _get_descriptors(self, sn, structure, tracer_atomic_number, soap_mask, soaper):
+        if isinstance(sn, SiteTrajectory):
+            sn = sn.site_network
+        assert isinstance(sn, SiteNetwork), "SOAPCenters requires a SiteNetwork or SiteTrajectory, not `%s`" % sn
+        return soaper(structure, sn.centers), np.arange(sn.n_sites)
+
+
+class SOAPSampledCenters(SOAPCenters):
+    """The SOAPs of representative points of every site, as ``sampling_transform`` makes them (``SOAP.py:169-192``):
+    ``sitator_amd.misc.NAvgsPerSite`` for a ``SiteTrajectory``, ``sitator_amd.misc.GenerateAroundSites`` for a ``SiteNetwork``.  The
+    transform must return a ``SiteNetwork`` whose ``site_types`` name the site a point was sampled from."""
+
+    def __init__(self, *args, **kwargs):
+        self.sampling_transform = kwargs.pop('sampling_transform', 1)
+        super(SOAPSampledCenters, self).__init__(*args, **kwargs)
+
+    def get_descriptors(self, stn):
+        sampled = self.sampling_transform.run(stn)
+        assert isinstance(sampled, SiteNetwork), "Sampling transform returned `%s`, not a SiteNetwork" % sampled
+        dvecs, _ = super(SOAPSampledCenters, self).get_descriptors(sampled)
+        return dvecs, sampled.site_types
+
+
+class SOAPDescriptorAverages(SOAP):
+    """Many instantaneous SOAPs per site, averaged in SOAP space (``SOAP.py:196-320``): one vector per assigned mobile ion per
+    strided frame, in the host structure as it was at that moment, ``averaging`` of them to an output vector.
+
+    ``stepsize``: stride in frames (1).  ``averaging``: vectors per output vector, or ``avg_descriptors_per_site``: the average
+    number of output vectors per site.  All environments of a call are evaluated and added up on the GPU
+    (``sit_soap_site_averages``); the vectors of an output row are added in ascending frame order, as the reference does."""
+
+    def __init__(self, *args, **kwargs):
+        averaging_key, stepsize_key, avg_desc_per_key = 'averaging', 'stepsize', 'avg_descriptors_per_site'
+        assert not ((averaging_key in kwargs) and (avg_desc_per_key in kwargs)), \
+            "`averaging` and `avg_descriptors_per_site` cannot be specified at the same time."
+        self._stepsize = kwargs.pop(stepsize_key, 1)
+        d = {stepsize_key: self._stepsize}
+        if averaging_key in kwargs:
+            self._averaging = kwargs.pop(averaging_key)
+            d[averaging_key] = self._averaging
+            self._avg_desc_per_site = None
+        elif avg_desc_per_key in kwargs:
+            self._avg_desc_per_site = kwargs.pop(avg_desc_per_key)
+            d[avg_desc_per_key] = self._avg_desc_per_site
+            self._averaging = None
+        else:
+            raise RuntimeError("Either the `averaging` or `avg_descriptors_per_site` option must be provided.")
+        for k, v in d.items():
+            if not isinstance(v, int):
+                raise TypeError('{} has to be an integer'.format(k))
+            if not (v > 0):
+                raise ValueError('{} has to be an positive'.format(k))
+        super(SOAPDescriptorAverages, self).__init__(*args, **kwargs)
+
+    def get_descriptors(self, st):
+        """From ``st.real_trajectory`` (host) and ``st``'s labels."""
+        assert isinstance(st, SiteTrajectory), "SOAPDescriptorAverages requires a SiteTrajectory"
+        if st.real_trajectory is None:
+            raise ValueError("SiteTrajectory must have associated real trajectory.")
+        real = np.asarray(st.real_trajectory)
+        if real.dtype != np.float64:
+            raise ValueError("Buffer dtype mismatch, expected 'double' but got '%s'" % real.dtype)
+        return self._averages(st, real)
+
+    def get_descriptors_for_analysis(self, la, st=None):
+        """The same from the frames a ``LandmarkAnalysis`` that has run left on its GPU: no upload (guards as
+        ``GenerateClampedTrajectory.run_for_analysis``; ``NotImplementedError`` after a run over frame shards)."""
+        st = resident_trajectory(la, st, "SOAPDescriptorAverages.get_descriptors_for_analysis")
+        return self._averages(st, None)
+
+    def _averages(self, st, positions):
+        if st._comm is not None and st._comm.size > 1:
+            raise NotImplementedError("SOAPDescriptorAverages needs all frames of the trajectory on one GPU; this trajectory is a "
+                                      "frame shard")
+        sn = st.site_network
+        structure, tracer_atomic_number, soap_mask, soaper = self._prepare(st)
+        nsit = int(sn.n_sites)
+        descs, counts, nr_of_descs, info = st._device().soap_site_averages(
+            nsit, np.where(soap_mask)[0], soaper.species_idx(structure.get_atomic_numbers()), np.where(sn.mobile_mask)[0], soaper.soap,
+            stepsize=self._stepsize, averaging=self._averaging, avg_descriptors_per_site=self._avg_desc_per_site, positions=positions)
+        if info["averaging"] == 0:
+            logger.warning("Asking for too many average descriptors per site; got averaging = 0; setting averaging = 1")
+        averaging = max(info["averaging"], 1)
+        logger.debug("Will average %i SOAP vectors for every output vector" % averaging)
+        insufficient = counts // averaging == 0
+        if np.any(insufficient):
+            logger.warning("You're asking to average %i SOAP vectors, but at this stepsize, %i sites are insufficiently occupied. "
+                           "Num occ./averaging: %s" % (averaging, np.sum(insufficient), counts[insufficient] / averaging))
+        self.last_info = info
+        return descs, np.repeat(np.arange(nsit), nr_of_descs)
