@@ -113,7 +113,8 @@ class SmoothSiteTrajectory(object):
     """Rolling-mode low-pass filter of every particle's site assignment.
 
     Args as the reference: ``window_threshold_factor`` (window width in units of the threshold),
-    ``remove_unoccupied_sites``, ``set_unassigned_under_threshold``.
+    ``remove_unoccupied_sites``, ``set_unassigned_under_threshold``.  On a frame shard the ranks exchange the frames a
+    window reaches over (``_run_on_shard``) and the result is the single-rank one, a shard again.
     """
 
     def __init__(self, window_threshold_factor=2.1, remove_unoccupied_sites=True, set_unassigned_under_threshold=True):
@@ -125,13 +126,15 @@ class SmoothSiteTrajectory(object):
         window = self.window_threshold_factor * threshold
         wleft, wright = int(np.floor(window / 2)), int(np.ceil(window / 2))
         n_sites = int(st.site_network.n_sites)
-        res = st._device().running_mode(wleft, wright, threshold, self.set_unassigned_under_threshold, n_sites=n_sites)
-        out, counts = res if n_sites > 0 else (res, np.zeros(0, dtype=np.int64))
+        comm = st._comm
+        if comm is not None and comm.size > 1:
+            out, counts = self._run_on_shard(st, comm, wleft, wright, threshold, n_sites)
+        else:
+            res = st._device().running_mode(wleft, wright, threshold, self.set_unassigned_under_threshold, n_sites=n_sites)
+            out, counts = res if n_sites > 0 else (res, np.zeros(0, dtype=np.int64))
         # a new trajectory around the smoothed labels (adopted, not copied: nothing else holds them), the confidences
         # shared as the reference's st.copy() shares them (SiteTrajectory.py:31-38 copies the assignments only)
-        new = type(st)(st.site_network.copy(), out, confidences=st._confs, _adopt=True)
-        if st._real_traj is not None:
-            new.set_real_traj(st._real_traj)
+        new = st._derive(st.site_network.copy(), out, st._confs)
         if self.remove_unoccupied_sites:
             # sites left without any assignment are dropped and the rest renumbered in order
             # (what the reference delegates to dynamics.RemoveUnoccupiedSites); which are left comes with the labels
@@ -155,6 +158,57 @@ class SmoothSiteTrajectory(object):
                 new._sn = newsn
         new.site_network.clear_attributes()
         return new
+
+    def _run_on_shard(self, st, comm, wleft, wright, threshold, n_sites):
+        """``(smoothed labels, visit counts)`` of a frame shard as the single-rank run gives them: the labels of this
+        rank's frames, the counts summed over the ranks.
+
+        The window of a frame reaches ``wleft`` frames back and ``wright - 1`` frames ahead, so every rank needs that many
+        frames of its neighbours.  One ``allgather`` carries every rank's frame count with its last ``wleft`` and first
+        ``wright - 1`` frames (bands of fixed size, padded where a rank is shorter); a rank collects its halo from as many
+        neighbours as it takes - a neighbour may hold fewer frames than the band, or none.  The mode runs on
+        ``[before | own | after]`` in a scratch context, so windows are clipped only where the whole trajectory ends and the
+        labels resident in the trajectory's own context (shared, perhaps, with the frames of a ``LandmarkAnalysis``) stay
+        the shard's."""
+        lab = np.ascontiguousarray(st._traj, dtype=np.int64)
+        n, M = lab.shape
+        nt, nh = wleft, max(wright - 1, 0)
+        msg = np.full((nt + nh) * M + 1, SiteTrajectory.SITE_UNKNOWN, dtype=np.int64)
+        msg[-1] = n
+        bands = msg[:-1].reshape(nt + nh, M)
+        tail, head = lab[n - min(n, nt):], lab[:min(n, nh)]
+        bands[nt - len(tail):nt] = tail                         # the tail band ends with the rank's last frame
+        bands[nt:nt + len(head)] = head                         # the head band starts with its first
+        every = comm.allgather(msg)
+        n_of = every[:, -1]
+        bands_of = every[:, :-1].reshape(comm.size, nt + nh, M)
+        before, after = [], []
+        need = nt
+        for r in range(comm.rank - 1, -1, -1):
+            k = min(need, int(n_of[r]))
+            before.insert(0, bands_of[r, nt - k:nt])
+            need -= k
+        need = nh
+        for r in range(comm.rank + 1, comm.size):
+            k = min(need, int(n_of[r]))
+            after.append(bands_of[r, nt:nt + k])
+            need -= k
+        ext = np.concatenate(before + [lab] + after)
+        nb = sum(len(b) for b in before)
+        device = st._ctx.device if st._ctx is not None else None
+        scratch = _lib.HipContext(np.asarray(st.site_network.structure.cell, dtype=np.float64), device=device)
+        try:
+            scratch.set_assignments(ext)
+            res = scratch.running_mode(wleft, wright, threshold, self.set_unassigned_under_threshold, n_sites=n_sites)
+        finally:
+            scratch.close()
+        if n_sites == 0:
+            return np.ascontiguousarray(res[nb:nb + n]), np.zeros(0, dtype=np.int64)
+        out, counts = res
+        # the counts came with the labels, the halo's included: those few frames are taken off again
+        for halo in (out[:nb], out[nb + n:]):
+            counts = counts - np.bincount(halo[halo >= 0], minlength=n_sites)
+        return np.ascontiguousarray(out[nb:nb + n]), comm.allreduce_sum(counts)
 
 
 class MergeSitesByDynamics(MergeSites):
@@ -311,9 +365,7 @@ class RemoveUnoccupiedSites(object):
                                                 n_mobile=old_sn.n_mobile)
         translation = np.full(n_sites + 1, SiteTrajectory.SITE_UNKNOWN, dtype=np.int64)   # [-1]: unknown stays unknown
         translation[:-1][seen_mask] = np.arange(n_new_sites)
-        new_st = SiteTrajectory(old_sn[seen_mask], translation[st._traj], confidences=None, _adopt=True)
-        if st.real_trajectory is not None:
-            new_st.set_real_traj(st.real_trajectory)
+        new_st = st._derive(old_sn[seen_mask], translation[st._traj], None)
         if return_kept_sites:
             return new_st, np.where(seen_mask)
         return new_st
@@ -464,10 +516,7 @@ class ReplaceUnassignedPositions(object):
         # :114-117 (see the class docstring for what the reference's copy keeps)
         new_sn = sn.copy(with_computed=False)
         new_sn.clear_attributes()
-        new = type(st)(new_sn, out, confidences=st._confs, _adopt=True)
-        if st._real_traj is not None:
-            new.set_real_traj(st._real_traj)
-        return new
+        return st._derive(new_sn, out, st._confs)
 
 
 class AverageVibrationalFrequency(object):

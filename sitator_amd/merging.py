@@ -96,9 +96,7 @@ class MergeSites(abc.ABC):
         unknown = labels == SiteTrajectory.SITE_UNKNOWN
         relabelled = np.where(unknown, SiteTrajectory.SITE_UNKNOWN, table[np.where(unknown, 0, labels)])
         # confidences describe the old assignment and are dropped (:118-120)
-        out = SiteTrajectory(merged, relabelled.astype(np.int64), confidences=None)
-        if st.real_trajectory is not None:
-            out.set_real_traj(st.real_trajectory)
+        out = st._derive(merged, relabelled.astype(np.int64), None)
         if self.set_merged_into:
             if old.has_attribute("merged_into"):
                 old.remove_attribute("merged_into")

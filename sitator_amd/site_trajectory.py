@@ -70,7 +70,8 @@ class SiteTrajectory(object):
 
     SITE_UNKNOWN = -1
 
-    def __init__(self, site_network, particle_assignments, confidences=None, _ctx=None, _comm=None, _adopt=False):
+    def __init__(self, site_network, particle_assignments, confidences=None, _ctx=None, _comm=None, _adopt=False,
+                 _frame0=0):
         particle_assignments = np.asarray(particle_assignments)
         if particle_assignments.ndim != 2:
             raise ValueError("particle_assignments must be 2D")
@@ -91,6 +92,18 @@ class SiteTrajectory(object):
         self._synced_version = _ctx.labels_version if _ctx is not None else -1
         self._host_shared = False
         self._comm = _comm
+        # Global number of this trajectory's first frame: not 0 on a frame shard.  A shared context knows it; a trajectory
+        # derived from a shard (`_derive`) has no context yet and uploads its labels with it (`_device`).
+        self._frame0 = int(_ctx.frame0 if _ctx is not None else _frame0)
+
+    def _derive(self, site_network, labels, confidences):
+        """A trajectory of other labels (adopted, not copied) for the same frames: the same communicator, first frame and
+        real trajectory - what an operator on a frame shard returns is a frame shard."""
+        st = type(self)(site_network, labels, confidences=confidences, _comm=self._comm, _adopt=True,
+                        _frame0=self._frame0)
+        if self._real_traj is not None:
+            st.set_real_traj(self._real_traj)
+        return st
 
     # -- container protocol ---------------------------------------------------------------
     def __len__(self):
@@ -100,10 +113,13 @@ class SiteTrajectory(object):
         st = type(self)(self._sn, self._traj[key], confidences=None if self._confs is None else self._confs[key])
         if self._real_traj is not None:
             st.set_real_traj(self._real_traj[key])
-        if isinstance(key, slice) and key == slice(None) and self._ctx is not None:
-            # a full copy starts with the same labels: it shares the device context (no upload while nothing moves)
-            st._ctx, st._comm = self._ctx, self._comm
-            st._synced_version = -1 if self._host_shared else self._synced_version
+        if isinstance(key, slice) and key == slice(None):
+            # a full copy is the same frames: of a frame shard, the same shard
+            st._comm, st._frame0 = self._comm, self._frame0
+            if self._ctx is not None:
+                # it starts with the same labels: it shares the device context (no upload while nothing moves)
+                st._ctx = self._ctx
+                st._synced_version = -1 if self._host_shared else self._synced_version
         return st
 
     def __getstate__(self):
@@ -140,7 +156,8 @@ class SiteTrajectory(object):
 
     @property
     def percent_unassigned(self):
-        return float(self.n_unassigned) / (self._sn.n_mobile * self.n_frames)
+        n = self._sn.n_mobile * self.n_frames
+        return float(self.n_unassigned) / n if n > 0 else 0.0         # (a frame shard may hold no frame)
 
     @property
     def site_network(self):
@@ -258,7 +275,7 @@ class SiteTrajectory(object):
         if ctx is None:
             cell = self._sn.structure.cell
             ctx = self._ctx = _lib.HipContext(np.asarray(cell, dtype=np.float64))
-            ctx.set_assignments(self._traj, self._confs)
+            ctx.set_assignments(self._traj, self._confs, frame0=self._frame0)
             ctx.labels_digest = (ctx.labels_version, _digest(self._traj)) if self._host_shared else None
         elif self._host_shared or ctx.labels_version != self._synced_version:
             d = (ctx.labels_version, _digest(self._traj))
@@ -287,8 +304,11 @@ class SiteTrajectory(object):
             first = int(np.argmin(keys[:, 0]))
             if keys[first, 0] != np.iinfo(np.int64).max:
                 frame, site = int(keys[first, 0]), int(keys[first, 1])
-                local = frame - ctx.frame0
-                mob = np.where(self._traj[local] == site)[0] if 0 <= local < self.n_frames else np.array([], dtype=int)
+                # the ions are known to the rank that holds the frame: everybody raises what that rank raises
+                mob = np.zeros(0, dtype=np.int64)
+                if comm.rank == first:
+                    mob = np.where(self._traj[frame - ctx.frame0] == site)[0].astype(np.int64)
+                mob = comm.bcast(mob, root=first)
                 raise errors.MultipleOccupancyError(mobile=mob, site=site, frame=frame)
             tot = comm.allreduce_sum(np.array([n_multi, total, nsites], dtype=np.int64))
             n_multi, total, nsites = (int(v) for v in tot)
