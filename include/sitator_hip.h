@@ -70,7 +70,7 @@ const char *sit_last_message(sit_ctx *ctx);
  * frame), out[5] = bytes of a communicator id (sit_comm_unique_id).  Writes min(n, 6) words and returns 6.  A binding
  * checks its own struct declarations against these once, at import (tests/test_abi.py does it for the ctypes stubs of
  * INTEGRATION.md and sitator_amd/_lib.py).  No context, no GPU needed.                                        */
-#define SIT_ABI_VERSION 12
+#define SIT_ABI_VERSION 13
 int sit_abi(int32_t *out, int n);
 /* Device buffers of 1 MB and more (the trajectory, the landmark rows, labels, the fit's arena) are kept by the process
  * when a context lets go of them, up to as much as its contexts have held at once, and handed to the next context that asks for a similar size: a process
@@ -548,6 +548,50 @@ int sit_soap_site_averages(sit_ctx *ctx, const double *positions, int64_t F, int
                            int64_t n_species, int64_t n_max, int64_t l_max, int crossover, const double *alpha, const double *beta,
                            int64_t n_dim, int64_t workspace_bytes, int64_t row_cap, int64_t *n_rows, int64_t *counts,
                            int64_t *nr_of_descs, double *descs, double *info4);
+
+/* ---- SiteTypeAnalysis (site_descriptors/SiteTypeAnalysis.py, which asks sklearn's PCA and pydpc) ---------------------------- */
+
+/* The plan of the density-peak entry points for points of d coordinates (csrc/dpc_plan.h), no context
+ * needed: out12 = {threads per workgroup, points per tile, digit bits and passes of the radix select, the largest d, LDS bytes per
+ * workgroup at this d, segments of the density and delta sums, the largest N; of the PCA entry points: rows per chunk, the edge of
+ * a workgroup's block of covariance entries, the largest D and N}.  SIT_ERR_INVALID: d < 1; SIT_ERR_CAPACITY: d > 32 (everything
+ * but the LDS bytes is set).                                                                                                   */
+int sit_dpc_plan(int64_t d, int64_t *out12);
+/* Column means and covariance of the rows X[N, D] (PCA.fit, SiteTypeAnalysis.py:83-84): mean[D] = sum / N, cov[D, D] = the sum
+ * over rows of (x - mean)(x - mean)^T / max(N - 1, 1), in float64.  Every sum runs in a fixed order (rows in chunks of 1024, a
+ * chunk's rows one by one, the chunks one by one; no atomics): the same bytes on every call, and cov is symmetric bit for bit.
+ * The eigen-decomposition of cov is the caller's (numpy.linalg.eigh).  SIT_ERR_INVALID: a missing array, N < 1 or D < 1, a value
+ * that is not finite or beyond 1e150; SIT_ERR_CAPACITY (the message names the limit): D > 4096, N > 2^25, chunk sums beyond
+ * 8 GiB.  Reads nothing of the context but its device and stream: frames, rows, labels and their validity stay as they are.    */
+int sit_pca_covariance(sit_ctx *ctx, const double *X, int64_t N, int64_t D, double *mean, double *cov);
+/* The projection Y[N, d] = (X - mean) comps^T for comps[d, D] (PCA.transform): Y[r, k] = the sum over ascending c of
+ * (X[r, c] - mean[c]) comps[k, c], one thread per entry.  Errors and context as sit_pca_covariance; d > 32 is SIT_ERR_CAPACITY. */
+int sit_pca_project(sit_ctx *ctx, const double *X, int64_t N, int64_t D, const double *mean, const double *comps, int64_t d,
+                    double *Y);
+/* What pydpc.Cluster(Y, fraction) computes (SiteTypeAnalysis.py:99) for the points Y[N, d], without its N x N distance matrix
+ * (csrc/dpc_plan.h; Rodriguez & Laio 2014; agreement with a pydpc installation is not claimed).  d(i, j) = sqrt(sum_k (y_ik -
+ * y_jk)^2), k ascending, no contraction.  *kernel_size = the distance of rank min(floor(0.5 + fraction n), n - 1) among the
+ * n = N (N - 1) / 2 distances i < j, found exactly by a radix select on the bit pattern (eight counting passes with integer
+ * atomics).  density[i] = sum over j != i of exp(-(d(i, j) / kernel_size)^2) in a fixed order (kernel_size 0: the number of points
+ * that coincide with i).  j is above i iff density[j] > density[i], or they are equal and j < i; delta[i] = the smallest distance
+ * to a point above i, neighbour[i] (int32) = that point, of equal distances the highest; the top point has neighbour -1 and the
+ * largest delta of the others.  The same bytes on every call.  info2 (optional) = {milliseconds from the first kernel to the last
+ * (HIP events; the eight 2 KiB read-backs of the select lie in between), n}.  SIT_ERR_INVALID: a missing array, N < 2, d < 1,
+ * fraction outside (0, 1), a coordinate that is not finite or beyond 1e150; SIT_ERR_CAPACITY (the message names the limit):
+ * d > 32, N > 2^24.  Reads nothing of the context but its device and stream.                                                  */
+int sit_dpc_graph(sit_ctx *ctx, const double *Y, int64_t N, int64_t d, double fraction, double *kernel_size, double *density,
+                  double *delta, int32_t *neighbour, double *info2);
+/* pydpc's Cluster.assign(min_density, min_delta) and the votes of SiteTypeAnalysis.py:143-147.  Centres are the points with
+ * density > min_density and delta > min_delta: clusters[N] (int32) receives their indices in ascending order, *n_clusters their
+ * number.  membership[N] (int32): a centre its number, every other point the membership of its neighbour, transitively (pointer
+ * jumping in rounds of plain launches); a chain that ends at a point that is no centre and has no neighbour gives -1.  votes
+ * (optional, with K > 0 and K * *n_clusters <= votes_cap): votes[K, *n_clusters] = the points of site dvecs_to_site[i] with
+ * membership m, counted with integer atomics.  SIT_ERR_INVALID: a missing array, N < 2, a density or delta that is not finite,
+ * a threshold that is NaN, a neighbour outside [-1, N) or chains that close on themselves, a site index outside [0, K);
+ * SIT_ERR_CAPACITY: N > 2^24.  Reads nothing of the context but its device and stream.                                        */
+int sit_dpc_assign(sit_ctx *ctx, const double *density, const double *delta, const int32_t *neighbour, int64_t N,
+                   double min_density, double min_delta, const int64_t *dvecs_to_site, int64_t K, int32_t *membership,
+                   int32_t *clusters, int64_t *n_clusters, int64_t *votes, int64_t votes_cap);
 
 /* ---- frame sharding across GPUs ------------------------------------ */
 

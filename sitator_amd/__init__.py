@@ -21,7 +21,7 @@ from .misc import GenerateAroundSites, NAvgsPerSite  # noqa: F401
 from .network import DiffusionPathwayAnalysis, MergeSitesByBarrier  # noqa: F401
 from .voronoi import VoronoiSiteGenerator  # noqa: F401
 from . import calculators  # noqa: F401
-from .site_descriptors import (InsufficientCoordinatingAtomsError, SiteVolumes, SOAP, SOAPCenters,  # noqa: F401
+from .site_descriptors import (InsufficientCoordinatingAtomsError, SiteTypeAnalysis, SiteVolumes, SOAP, SOAPCenters,  # noqa: F401
                                SOAPDescriptorAverages, SOAPSampledCenters, device_soap_backend)
 
 __version__ = "0.1.0"

@@ -40,7 +40,7 @@ class FillParams(C.Structure):
                    int(store_rows), int(assign), int(predict_normed), int(defer), float(predict_threshold))
 
 
-ABI_VERSION = 12         # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
+ABI_VERSION = 13       # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
 
 
 # every symbol include/sitator_hip.h declares: (restype, argtypes)
@@ -123,6 +123,11 @@ SIGNATURES = {
     "sit_soap_plan": (C.c_int, [_dp, C.c_double, i64, i64, i64, _ip]),
     "sit_soap_site_averages": (C.c_int, [_vp, _dp, i64, i64, _ip, _i32p, i64, _ip, i64, i64, i64, i64, i64, C.c_double, C.c_double,
                                          C.c_double, i64, i64, i64, C.c_int, _dp, _dp, i64, i64, i64, _ip, _ip, _ip, _dp, _dp]),
+    "sit_dpc_plan": (C.c_int, [i64, _ip]),
+    "sit_pca_covariance": (C.c_int, [_vp, _dp, i64, i64, _dp, _dp]),
+    "sit_pca_project": (C.c_int, [_vp, _dp, i64, i64, _dp, _dp, i64, _dp]),
+    "sit_dpc_graph": (C.c_int, [_vp, _dp, i64, i64, C.c_double, _dp, _dp, _dp, _i32p, _dp]),
+    "sit_dpc_assign": (C.c_int, [_vp, _dp, _dp, _i32p, i64, C.c_double, C.c_double, _ip, i64, _i32p, _i32p, _ip, _ip, i64]),
     "sit_comm_unique_id": (C.c_int, [_u8p]),
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
     "sit_comm_destroy": (C.c_int, [_vp]),
@@ -221,6 +226,21 @@ def soap_plan(cell, cutoff, n_species, n_max, l_max):
     plan = {"translations": tuple(int(v) for v in out[:3]), "threads": int(out[3]), "nbr_cap": int(out[4]), "lds_bytes": int(out[5]),
             "n_coef": int(out[9]), "n_dim": int(out[10]), "n_dim_crossover": int(out[11])}
     plan.update(limits)
+    return plan
+
+
+def dpc_plan(d=1):
+    """The plan of ``dpc_graph`` for points of ``d`` coordinates (``sit_dpc_plan``): the workgroup, the tile, the digits and passes
+    of the radix select, the limits and the LDS bytes.  Beyond the largest ``d``: ``RuntimeError``."""
+    out = np.zeros(12, dtype=np.int64)
+    rc = load().sit_dpc_plan(int(d), _i(out))
+    keys = ["threads", "tile", "digit_bits", "passes", "max_d", "lds_bytes", "segments", "max_n", "pca_rows", "pca_edge", "pca_max_d",
+            "pca_max_n"]
+    plan = {k: int(v) for k, v in zip(keys, out)}
+    if rc == E_CAPACITY:
+        raise RuntimeError("dpc_plan: more than %d coordinates per point" % plan["max_d"])
+    if rc != OK:
+        raise ValueError("dpc_plan: d must be at least 1")
     return plan
 
 
@@ -1055,6 +1075,62 @@ class HipContext(object):
         return descs, counts, nr, {"kernel_ms": float(info[0]), "contributors": int(info[1]), "chunks": int(info[2]),
                                    "averaging": int(info[3])}
 
+    # -- SiteTypeAnalysis: PCA statistics and density-peak clustering; they read nothing of the context but its device
+    def pca_covariance(self, X):
+        """``(mean [D], cov [D, D])`` of the rows ``X`` ``[N, D]`` (``sit_pca_covariance``): ``cov`` has the divisor
+        ``max(N - 1, 1)``.  Beyond a capacity ``RuntimeError``, anything else that does not fit ``ValueError``."""
+        X = _f64(X)
+        assert X.ndim == 2
+        N, D = X.shape
+        mean, cov = np.zeros(D), np.zeros((D, D))
+        self._check(self.lib.sit_pca_covariance(self._h, _d(X), N, D, _d(mean), _d(cov)))
+        return mean, cov
+
+    def pca_project(self, X, mean, components):
+        """``Y [N, d] = (X - mean) @ components.T`` for ``components`` ``[d, D]`` (``sit_pca_project``)."""
+        X, mean, components = _f64(X), _f64(mean).reshape(-1), _f64(components)
+        assert X.ndim == 2 and components.ndim == 2 and components.shape[1] == X.shape[1] == len(mean)
+        N, D = X.shape
+        d = components.shape[0]
+        Y = np.zeros((N, d))
+        self._check(self.lib.sit_pca_project(self._h, _d(X), N, D, _d(mean), _d(components), d, _d(Y)))
+        return Y
+
+    def dpc_graph(self, Y, fraction=0.02):
+        """``(kernel_size, density [N], delta [N], neighbour int32 [N], info)`` (``sit_dpc_graph``): what ``pydpc.Cluster(Y,
+        fraction)`` computes for the points ``Y`` ``[N, d]``, by the definitions of ``csrc/dpc_plan.h``.  ``info``: the kernel
+        milliseconds and the number of pairs."""
+        Y = _f64(Y)
+        assert Y.ndim == 2
+        N, d = Y.shape
+        ks = C.c_double(0.0)
+        density, delta, nbr, info = np.zeros(N), np.zeros(N), np.zeros(N, dtype=np.int32), np.zeros(2)
+        self._check(self.lib.sit_dpc_graph(self._h, _d(Y), N, d, float(fraction), C.byref(ks), _d(density), _d(delta),
+                                           nbr.ctypes.data_as(_i32p), _d(info)))
+        return ks.value, density, delta, nbr, {"kernel_ms": float(info[0]), "pairs": int(info[1])}
+
+    def dpc_assign(self, density, delta, neighbour, min_density, min_delta, dvecs_to_site=None, K=0):
+        """``(membership int32 [N], clusters int32 [n_clusters], votes int64 [K, n_clusters] or None)`` (``sit_dpc_assign``):
+        centres are the points with ``density > min_density`` and ``delta > min_delta``, every other point follows its neighbour;
+        ``votes[s, m]`` counts the points of site ``dvecs_to_site[i] == s`` with membership ``m``."""
+        density, delta = _f64(density).reshape(-1), _f64(delta).reshape(-1)
+        neighbour = np.ascontiguousarray(neighbour, dtype=np.int32).reshape(-1)
+        N = len(density)
+        assert len(delta) == N == len(neighbour)
+        K = int(K) if dvecs_to_site is not None else 0
+        site = _i64(dvecs_to_site).reshape(-1) if dvecs_to_site is not None else None
+        assert site is None or len(site) == N
+        membership, clusters = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.int32)
+        nc = i64(0)
+        guess = int(np.count_nonzero((density > min_density) & (delta > min_delta)))
+        votes = np.zeros((K, guess), dtype=np.int64) if K > 0 else None
+        self._check(self.lib.sit_dpc_assign(self._h, _d(density), _d(delta), neighbour.ctypes.data_as(_i32p), N, float(min_density),
+                                            float(min_delta), None if site is None else _i(site), K,
+                                            membership.ctypes.data_as(_i32p), clusters.ctypes.data_as(_i32p), C.byref(nc),
+                                            None if votes is None else _i(votes), 0 if votes is None else votes.size))
+        assert int(nc.value) == guess
+        return membership, clusters[:guess].copy(), votes
+
     # ---- RCCL exchange of the frame-sharded path (csrc/comm.hip) ----
     def comm_create(self, unique_id, rank, world):
         uid = np.frombuffer(bytes(unique_id), dtype=np.uint8).copy()
@@ -1179,6 +1255,7 @@ for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "a
               "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
               "unknown_runs", "replace_closer", "clamp_trajectory", "group_by_site", "grouped_fetch", "grouped_bucket_averages",
               "grouped_recenter_step", "grouped_hull_volumes", "grouped_work_fetch", "min_image", "pathway_components",
-              "barrier_energies", "voronoi_nodes", "soap_vectors", "soap_site_averages"):
+              "barrier_energies", "voronoi_nodes", "soap_vectors", "soap_site_averages", "pca_covariance", "pca_project", "dpc_graph",
+              "dpc_assign"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

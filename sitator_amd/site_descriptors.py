@@ -4,6 +4,10 @@
 ``device_soap_backend``: the power spectrum of DESIGN.md section 17, evaluated on the GPU (``sit_soap_vectors``,
 ``sit_soap_site_averages``).  The reference's QUIP and DScribe backends are not carried and there is no host fallback.
 
+``SiteTypeAnalysis`` (reference: ``sitator/site_descriptors/SiteTypeAnalysis.py``): PCA of the descriptor vectors, density-peak
+clustering of the projections and a vote per site, by the definitions of DESIGN.md section 18 (``sit_pca_covariance``,
+``sit_pca_project``, ``sit_dpc_graph``, ``sit_dpc_assign``) instead of sklearn and pydpc.
+
 ``SiteVolumes`` (reference: ``sitator/site_descriptors/SiteVolumes.py``): the recentring of every site's point cloud runs on
 the GPU for all sites at once (``sit_grouped_recenter_step``); the convex hulls are qhull's on the host (``hulls="host"``, the
 default) or the device's (``hulls="device"``: ``sit_grouped_hull_volumes``, with qhull for the sites it flags)."""
@@ -448,3 +452,168 @@ class SOAPDescriptorAverages(SOAP):
                            "Num occ./averaging: %s" % (averaging, np.sum(insufficient), counts[insufficient] / averaging))
         self.last_info = info
         return descs, np.repeat(np.arange(nsit), nr_of_descs)
+
+
+# ---- SiteTypeAnalysis ----------------------------------------------------------------------------------------------------------
+
+class DescriptorPCA(object):
+    """What ``SiteTypeAnalysis`` keeps of its PCA, under sklearn's names: ``components_`` ``[d, D]``, ``explained_variance_``,
+    ``explained_variance_ratio_`` (of the ``d`` components taken), ``mean_``, ``n_components_``."""
+
+    def __init__(self, mean, components, explained_variance, explained_variance_ratio):
+        self.mean_ = mean
+        self.components_ = components
+        self.explained_variance_ = explained_variance
+        self.explained_variance_ratio_ = explained_variance_ratio
+        self.n_components_ = len(components)
+
+
+def pca_from_covariance(mean, cov, n_samples, min_pca_variance, min_pca_dimensions):
+    """The host side of the PCA: sklearn's ``PCA(min_pca_variance)`` rule on the eigenvalues of ``cov`` (divisor
+    ``n_samples - 1``) - ``n_components = searchsorted(cumsum(ratio), min_pca_variance, side="right") + 1`` over the
+    ``min(n_samples, D)`` components a full SVD would give - and ``min_pca_dimensions`` components when fewer come out
+    (``SiteTypeAnalysis.py:83-90``).  Column signs are ``numpy.linalg.eigh``'s: distances do not see them."""
+    cov = np.asarray(cov, dtype=np.float64)
+    D = cov.shape[0]
+    w, v = np.linalg.eigh(cov)
+    w, v = np.maximum(w[::-1], 0.0), v[:, ::-1]
+    n_full = min(int(n_samples), D)
+    w, v = w[:n_full], v[:, :n_full]
+    ratio = w / np.sum(w)
+    if not 0.0 < min_pca_variance < 1.0:
+        raise ValueError("min_pca_variance must be in (0, 1), not %r" % (min_pca_variance,))
+    n_components = int(np.searchsorted(np.cumsum(ratio), min_pca_variance, side="right")) + 1
+    if n_components < min_pca_dimensions:
+        logger.info("     PCA accounted for %.0f%% variance in only %i dimensions; less than minimum of %.0f."
+                    % (100.0 * np.sum(ratio[:n_components]), n_components, min_pca_dimensions))
+        logger.info("     Forcing PCA to use %i dimensions." % min_pca_dimensions)
+        n_components = int(min_pca_dimensions)
+    if not 1 <= n_components <= n_full:
+        raise ValueError("n_components=%r must be between 1 and min(n_samples, n_features)=%r" % (n_components, n_full))
+    return DescriptorPCA(np.asarray(mean, dtype=np.float64), np.ascontiguousarray(v[:, :n_components].T), w[:n_components],
+                         ratio[:n_components])
+
+
+class DensityPeaks(object):
+    """Density-peak clustering of ``points`` ``[N, d]`` on the GPU (``sit_dpc_graph``, ``sit_dpc_assign``), under the attribute
+    names of ``pydpc.Cluster``: ``kernel_size``, ``density``, ``delta``, ``neighbour``, ``order`` (densest first), and after
+    ``assign(min_density, min_delta)`` ``clusters`` and ``membership``.  The definitions are those of ``csrc/dpc_plan.h``
+    (DESIGN.md section 18); pydpc's halo and border are not carried."""
+
+    def __init__(self, points, fraction=0.02, ctx=None):
+        self.points = np.ascontiguousarray(points, dtype=np.float64)
+        self.npoints = len(self.points)
+        self.fraction = fraction
+        self._ctx = ctx
+        self.kernel_size, self.density, self.delta, self.neighbour, self.info = ctx.dpc_graph(self.points, fraction)
+        # densest first, equal densities by ascending index: the order `above` of the plan
+        self.order = np.lexsort((np.arange(self.npoints), -self.density)).astype(np.int32)
+        self.clusters = self.membership = self.votes = None
+
+    def assign(self, min_density, min_delta, dvecs_to_site=None, n_sites=0):
+        self.min_density, self.min_delta = min_density, min_delta
+        self.membership, self.clusters, self.votes = self._ctx.dpc_assign(self.density, self.delta, self.neighbour, min_density,
+                                                                          min_delta, dvecs_to_site, n_sites)
+        self.nclusters = len(self.clusters)
+
+
+class SiteTypeAnalysis(object):
+    """Cluster sites into types using a continuous descriptor and Density Peak Clustering (``SiteTypeAnalysis.py``).
+
+    Computes descriptor vectors, reduces them with a principal component analysis and clusters them with density-peak
+    clustering; every site gets the type most of its descriptor vectors were assigned to.  The column statistics, the projection,
+    the clustering and the vote run on the GPU (``sit_pca_covariance``, ``sit_pca_project``, ``sit_dpc_graph``,
+    ``sit_dpc_assign``); there is no host fallback.
+
+    ``descriptor``: anything with ``get_descriptors(st|sn)`` returning descriptor vectors ``(M, n_dim)`` and the site of each.
+    ``min_pca_variance``: the proportion of the variance the taken components must explain.  ``min_pca_dimensions``: take at
+    least this many.  ``n_site_types_max``: the largest number of clusters; must be reasonable for the automatic choice to work.
+    The plot methods of the reference are not carried."""
+
+    def __init__(self, descriptor, min_pca_variance=0.9, min_pca_dimensions=2, n_site_types_max=20):
+        self.descriptor = descriptor
+        self.min_pca_variance = min_pca_variance
+        self.min_pca_dimensions = min_pca_dimensions
+        self.n_site_types_max = n_site_types_max
+        self._n_dvecs = None
+
+    def run(self, descriptor_input, **kwargs):
+        """``descriptor_input``: a ``SiteNetwork`` or ``SiteTrajectory``; returns a copy of the network with ``site_types``."""
+        from .elbow import index_of_elbow
+        if self._n_dvecs is not None:
+            raise ValueError("Can't run SiteTypeAnalysis more than once!")
+        logger.info(" -- Running SiteTypeAnalysis --")
+        if isinstance(descriptor_input, SiteNetwork):
+            sn = descriptor_input.copy()
+        elif isinstance(descriptor_input, SiteTrajectory):
+            if descriptor_input._comm is not None and descriptor_input._comm.size > 1:
+                raise NotImplementedError("SiteTypeAnalysis needs the descriptors of the whole trajectory on one GPU; this "
+                                          "trajectory is a frame shard")
+            sn = descriptor_input.site_network.copy()
+        else:
+            raise RuntimeError("Input {}".format(type(descriptor_input)))
+
+        logger.info("  - Computing Descriptor Vectors")
+        self.dvecs, dvecs_to_site = self.descriptor.get_descriptors(descriptor_input, **kwargs)
+        assert len(self.dvecs) == len(dvecs_to_site), "Length mismatch in descriptor return values"
+        dvecs_to_site = np.asarray(dvecs_to_site, dtype=np.int64)
+        assert np.min(dvecs_to_site) == 0 and np.max(dvecs_to_site) < sn.n_sites
+
+        logger.info("  - Clustering Descriptor Vectors")
+        ctx = _lib.HipContext(np.asarray(sn.structure.cell, dtype=np.float64))
+        try:
+            dvecs = np.ascontiguousarray(self.dvecs, dtype=np.float64)
+            mean, cov = ctx.pca_covariance(dvecs)
+            self.pca = pca_from_covariance(mean, cov, len(dvecs), self.min_pca_variance, self.min_pca_dimensions)
+            self.dvecs = ctx.pca_project(dvecs, self.pca.mean_, self.pca.components_)
+            logger.info("     Accounted for %.0f%% of variance in %i dimensions"
+                        % (100.0 * np.sum(self.pca.explained_variance_ratio_), self.dvecs.shape[1]))
+
+            self.dpc = DensityPeaks(self.dvecs, ctx=ctx)
+            # the sorted density * delta plot (fig. 4 of the paper): its elbow is, more or less, the number of clusters
+            decision_curve = self.dpc.density * self.dpc.delta
+            decision_curve_sort = np.argsort(decision_curve)[::-1]
+            decision_curve = decision_curve[decision_curve_sort[:int(self.n_site_types_max * 1.5)]]
+            elbow = index_of_elbow(decision_curve)
+            self._decision_curve = decision_curve
+            self._decision_elbow = elbow
+            if elbow == 0:
+                raise ValueError("Something went wrong with the decision curve (elbow == 0); try more data.")
+            # a little less than the minimum in both cases
+            density_threshold = np.min(self.dpc.density[decision_curve_sort[:elbow]]) - 0.001
+            delta_threshold = np.min(self.dpc.delta[decision_curve_sort[:elbow]]) - 0.001
+            self._real_dpc_thresh = (density_threshold, delta_threshold)
+            self.dpc.assign(density_threshold, delta_threshold, dvecs_to_site, sn.n_sites)
+        finally:
+            if getattr(self, "dpc", None) is not None:
+                self.dpc._ctx = None                                 # the context goes; what was computed stays
+            ctx.close()
+        assignments = self.dpc.membership
+        unassigned = assignments < 0
+        self._n_unassigned = np.sum(unassigned)
+        self._n_dvecs = len(self.dvecs)
+        site_type_counts = np.bincount(assignments[~unassigned])
+        self.n_types = len(self.dpc.clusters)
+        assert self.n_types == len(site_type_counts), "Got %i types from the clustering, but counted %i" % (self.n_types,
+                                                                                                          len(site_type_counts))
+        logger.info("     Found %i site type clusters" % self.n_types)
+        logger.info("     Failed to assign %i/%i descriptor vectors to clusters." % (self._n_unassigned, self._n_dvecs))
+
+        # -- voting: votes[site, type] were counted on the device
+        votes = self.dpc.votes
+        n_votes = np.bincount(dvecs_to_site, minlength=sn.n_sites)
+        types = np.empty(shape=sn.n_sites, dtype=np.int64)
+        self.winning_vote_percentages = np.empty(shape=sn.n_sites, dtype=np.float64)
+        for site in range(sn.n_sites):
+            if votes is None or votes.shape[1] == 0 or not votes[site].any():
+                raise ValueError("No votes for site %i; check clustering and descriptors." % site)
+            winner = np.argmax(votes[site])
+            self.winning_vote_percentages[site] = float(votes[site, winner]) / n_votes[site]
+            types[site] = winner
+        n_sites_of_each_type = np.bincount(types, minlength=self.n_types)
+        sn.site_types = types
+        logger.info(("             " + "Type {:<2} " * self.n_types).format(*range(self.n_types)))
+        logger.info(("# of sites   " + "{:<8}" * self.n_types).format(*n_sites_of_each_type))
+        if np.any(n_sites_of_each_type == 0):
+            logger.warning("WARNING: Had site types with no sites; check clustering settings/voting!")
+        return sn
