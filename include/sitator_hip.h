@@ -501,6 +501,37 @@ int sit_voronoi_nodes(sit_ctx *ctx, const double *static_pos, int64_t S, double 
  * record, 1 / VP_SHAPE_MIN}; radius2 (optional) = {the first search radius, the growth factor}.                             */
 int sit_voronoi_plan(const double *cell, int64_t S, int64_t *out8, double *radius2);
 
+/* ---- Coordination environments of sites (site_descriptors/SiteCoordinationEnvironment.py, which asks pymatgen's ChemEnv) ------ */
+
+/* For each of centers[K, 3], alone with static_pos[S, 3] and all its periodic images under the context's cell
+ * (csrc/coordenv_plan.h): the static images that coordinate the site - the face neighbours of the site's Voronoi cell (certified
+ * empty spheres through the site, tolerance tau) with distance / smallest distance <= distance_cutoff and solid angle / largest
+ * solid angle >= angle_cutoff - and the continuous shape measure S (0 - 100, Pinsky & Avnir) of their polyhedron, the site at the
+ * origin, against every library shape of that coordination number, minimised over all n! vertex assignments.  Two-call
+ * convention: every call sets *n_indices, status[K] (0 done, 1 the search radius would have to grow further, 2 an uncertain test
+ * was met or an atom lies on the site, 3 a capacity of sit_coordenv_plan was exceeded), flags[K] (bit 0: a ratio within 1e-9
+ * relative of its cutoff; the comparison still decided), n[K] (coordinating images), shape[K] (library index of the environment:
+ * the smallest S if below max_csm, else -1), csm_best[K] (NaN without a library shape), csm_all[K, 3] (the shapes of that n in
+ * library order, NaN padded), confidence[K] (w_best / sum w, w = (1 - S / max_csm)^2 below max_csm) and info8 = {rounds of the
+ * search radius, the last radius, the largest neighbour count, the largest n, milliseconds of k_coordenv_cell and of
+ * k_coordenv_csm (HIP events), the first radius, 1 if this call computed and 0 if it returned the kept result}; when
+ * n_indices <= index_cap it also fills the CSR offsets[K + 1], indices[n_indices] (static index; ordered by distance, static
+ * index, image; an index repeats when two images of one atom coordinate), norm_distance and norm_angle.  The result of the last
+ * call is kept with the context: the fill call after a size call with the same input computes nothing.  Nothing depends on
+ * arrival: the same bytes on every call.  Every output but n_indices is optional.  SIT_ERR_INVALID: a missing array, S < 1,
+ * K < 1, tau or max_csm not positive, distance_cutoff < 1, angle_cutoff outside (0, 1], a degenerate cell, a value that is not
+ * finite or a position more than 2^20 cells from the origin; SIT_ERR_CAPACITY: 2^24 atoms or sites, or more.  Reads nothing of the
+ * context but its cell, device and stream.                                                                                    */
+int sit_coordination_environments(sit_ctx *ctx, const double *static_pos, int64_t S, const double *centers, int64_t K, double tau,
+                                  double distance_cutoff, double angle_cutoff, double max_csm, int64_t index_cap, int64_t *n_indices,
+                                  int32_t *status, int32_t *flags, int32_t *n, int64_t *offsets, int32_t *indices, double *norm_distance,
+                                  double *norm_angle, int32_t *shape, double *csm_best, double *csm_all, double *confidence, double *info8);
+/* The plan of sit_coordination_environments, no context needed: out8 = {neighbour cap, cell vertices per site, vertices per face,
+ * coordinating images per site, the largest n with a shape measure, threads per workgroup, LDS bytes of the cell kernel, shapes
+ * in the library}; shape_n[12] (optional) the coordination number of each library shape (S:1, L:2, TL:3, T:4, S:4, T:5, S:5, O:6,
+ * T:6, PB:7, C:8, SA:8, in this order); coords[12, 8, 3] (optional) their unit vertices, rows beyond n zero.                   */
+int sit_coordenv_plan(int64_t *out8, int32_t *shape_n, double *coords);
+
 /* ---- SOAP site descriptors (site_descriptors/SOAP.py, which asks QUIP or DScribe) --------------------------------------------- */
 
 /* The SOAP power spectrum of every centre of centers[P, 3] in the lattice static_pos[S, 3] under the context's cell

@@ -6,7 +6,7 @@ Host code is Python and talks to hand-written HIP kernels (gfx950) through the c
     from sitator_amd import SiteNetwork, SiteTrajectory, LandmarkAnalysis
     st = LandmarkAnalysis(clustering_algorithm="dotprod").run(sn, frames)
 """
-from .errors import (InsufficientSitesError, LandmarkAnalysisError, MultipleOccupancyError,  # noqa: F401
+from .errors import (CoordinationEnvironmentError, InsufficientSitesError, LandmarkAnalysisError, MultipleOccupancyError,  # noqa: F401
                      StaticLatticeError, VoronoiError, ZeroLandmarkError)
 from .site_network import SiteNetwork, Structure  # noqa: F401
 from .site_trajectory import SiteGrouping, SiteTrajectory  # noqa: F401
@@ -21,7 +21,8 @@ from .misc import GenerateAroundSites, NAvgsPerSite  # noqa: F401
 from .network import DiffusionPathwayAnalysis, MergeSitesByBarrier  # noqa: F401
 from .voronoi import VoronoiSiteGenerator  # noqa: F401
 from . import calculators  # noqa: F401
-from .site_descriptors import (InsufficientCoordinatingAtomsError, SiteTypeAnalysis, SiteVolumes, SOAP, SOAPCenters,  # noqa: F401
-                               SOAPDescriptorAverages, SOAPSampledCenters, device_soap_backend)
+from .site_descriptors import (InsufficientCoordinatingAtomsError, SiteCoordinationEnvironment, SiteTypeAnalysis, SiteVolumes, SOAP,  # noqa: F401
+                               SOAPCenters, SOAPDescriptorAverages, SOAPSampledCenters, device_soap_backend)
+from .descriptors import ConfigurationalEntropy  # noqa: F401
 
 __version__ = "0.1.0"

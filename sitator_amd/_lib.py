@@ -118,6 +118,9 @@ SIGNATURES = {
     "sit_barrier_plan": (C.c_int, [_dp, C.c_double, _ip]),
     "sit_voronoi_nodes": (C.c_int, [_vp, _dp, i64, C.c_double, i64, i64, _ip, _ip, _dp, _dp, _ip, _i32p, _i32p, _i32p, _dp]),
     "sit_voronoi_plan": (C.c_int, [_dp, i64, _ip, _dp]),
+    "sit_coordination_environments": (C.c_int, [_vp, _dp, i64, _dp, i64, C.c_double, C.c_double, C.c_double, C.c_double, i64, _ip, _i32p,
+                                                _i32p, _i32p, _ip, _i32p, _dp, _dp, _i32p, _dp, _dp, _dp, _dp]),
+    "sit_coordenv_plan": (C.c_int, [_ip, _i32p, _dp]),
     "sit_soap_vectors": (C.c_int, [_vp, _dp, _i32p, i64, _dp, i64, C.c_double, C.c_double, C.c_double, i64, i64, i64, C.c_int, _dp, _dp,
                                    i64, _dp, _i32p]),
     "sit_soap_plan": (C.c_int, [_dp, C.c_double, i64, i64, i64, _ip]),
@@ -254,6 +257,23 @@ def voronoi_plan(cell, S):
     keys = ["neighbour_cap", "record_cap", "member_cap", "threads", "lds_bytes", "max_rounds", "record_bytes", "inverse_shape_min"]
     plan = {k: int(v) for k, v in zip(keys, out)}
     plan["first_radius"], plan["growth"] = float(rad[0]), float(rad[1])
+    return plan
+
+
+COORDENV_SHAPES = ("S:1", "L:2", "TL:3", "T:4", "S:4", "T:5", "S:5", "O:6", "T:6", "PB:7", "C:8", "SA:8")   # library order
+
+
+def coordenv_plan():
+    """The plan of ``coordination_environments`` (``sit_coordenv_plan``): the caps, the workgroup, and the shape library as
+    ``"symbols"``, ``"shape_n"`` and ``"shapes"`` (a list of ``[n, 3]`` unit vertices)."""
+    out, sn, co = np.zeros(8, dtype=np.int64), np.zeros(len(COORDENV_SHAPES), dtype=np.int32), np.zeros((len(COORDENV_SHAPES), 8, 3))
+    if load().sit_coordenv_plan(_i(out), sn.ctypes.data_as(_i32p), _d(co)) != OK:
+        raise ValueError("coordenv_plan")
+    keys = ["neighbour_cap", "vertex_cap", "face_cap", "coordination_cap", "max_n", "threads", "lds_bytes", "n_shapes"]
+    plan = {k: int(v) for k, v in zip(keys, out)}
+    assert plan["n_shapes"] == len(COORDENV_SHAPES)
+    plan["symbols"], plan["shape_n"] = list(COORDENV_SHAPES), [int(v) for v in sn]
+    plan["shapes"] = [co[s, :sn[s]].copy() for s in range(len(COORDENV_SHAPES))]
     return plan
 
 
@@ -1017,6 +1037,36 @@ class HipContext(object):
         return {"centers": centers, "radii": radii, "vertices": [indices[offsets[j]:offsets[j + 1]].copy() for j in range(n)],
                 "status": status, "nbr_count": nbr, "info": out_info}
 
+    # -- SiteCoordinationEnvironment: reads nothing of the context but its cell
+    def coordination_environments(self, static_pos, centers, tau=1e-6, distance_cutoff=1.4, angle_cutoff=0.3, max_csm=8.0):
+        """``{"status", "flags", "n", "shape" int32 [K], "vertices" (list of K int arrays: static indices of the coordinating
+        images, ordered by distance, static index, image), "norm_distance", "norm_angle" (lists of K arrays), "csm_best" [K],
+        "csm_all" [K, 3], "confidence" [K], "info" dict}`` (``sit_coordination_environments``, size call then fill call) for the
+        sites ``centers`` ``[K, 3]`` among ``static_pos`` ``[S, 3]`` under the context's cell."""
+        static_pos, centers = _f64(static_pos).reshape(-1, 3), _f64(centers).reshape(-1, 3)
+        S, K = len(static_pos), len(centers)
+        i32 = lambda: np.zeros(max(K, 1), dtype=np.int32)
+        status, flags, n, shape = i32(), i32(), i32(), i32()
+        best, call, conf, info = np.zeros(max(K, 1)), np.zeros((max(K, 1), 3)), np.zeros(max(K, 1)), np.zeros(8)
+        ni = i64(0)
+        head = (self._h, _d(static_pos), S, _d(centers), K, float(tau), float(distance_cutoff), float(angle_cutoff), float(max_csm))
+        per = (status.ctypes.data_as(_i32p), flags.ctypes.data_as(_i32p), n.ctypes.data_as(_i32p))
+        tail = (shape.ctypes.data_as(_i32p), _d(best), _d(call), _d(conf), _d(info))
+        self._check(self.lib.sit_coordination_environments(*head, 0, C.byref(ni), *per, None, None, None, None, *tail))
+        computed = int(info[7])
+        m = int(ni.value)
+        offsets, indices = np.zeros(K + 1, dtype=np.int64), np.zeros(max(m, 1), dtype=np.int32)
+        nd, na = np.zeros(max(m, 1)), np.zeros(max(m, 1))
+        self._check(self.lib.sit_coordination_environments(*head, m, C.byref(ni), *per, _i(offsets), indices.ctypes.data_as(_i32p), _d(nd),
+                                                           _d(na), *tail))
+        assert int(ni.value) == m
+        keys = ["rounds", "final_radius", "max_neighbours", "max_n", "cell_ms", "csm_ms", "first_radius", "fill_computed"]
+        out_info = {k: (int(v) if k in ("rounds", "max_neighbours", "max_n", "fill_computed") else float(v)) for k, v in zip(keys, info)}
+        out_info["size_computed"] = computed
+        cut = lambda a: [a[offsets[j]:offsets[j + 1]].copy() for j in range(K)]
+        return {"status": status[:K], "flags": flags[:K], "n": n[:K], "shape": shape[:K], "vertices": cut(indices), "norm_distance": cut(nd),
+                "norm_angle": cut(na), "csm_best": best[:K], "csm_all": call[:K], "confidence": conf[:K], "info": out_info}
+
     # -- SOAP descriptors: soap_vectors reads nothing of the context but its cell, soap_site_averages labels and frames only
     def _soap_args(self, soap):
         """The tail of scalars and tables the SOAP entry points share, from a ``soap`` dict (``site_descriptors.soap_tables``), and
@@ -1255,7 +1305,7 @@ for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "a
               "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
               "unknown_runs", "replace_closer", "clamp_trajectory", "group_by_site", "grouped_fetch", "grouped_bucket_averages",
               "grouped_recenter_step", "grouped_hull_volumes", "grouped_work_fetch", "min_image", "pathway_components",
-              "barrier_energies", "voronoi_nodes", "soap_vectors", "soap_site_averages", "pca_covariance", "pca_project", "dpc_graph",
+              "barrier_energies", "voronoi_nodes", "coordination_environments", "soap_vectors", "soap_site_averages", "pca_covariance", "pca_project", "dpc_graph",
               "dpc_assign"):
     setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
 del _name

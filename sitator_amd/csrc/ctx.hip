@@ -247,6 +247,7 @@ extern "C" void sit_destroy(sit_ctx *c)
     spectrum_free(c);
     group_free(c);
     voronoi_free(c);
+    coordenv_free(c);
     fill_ring_free(c);
     stream_give(c->device, 1, c->copy_stream);
     stream_give(c->device, 2, c->copy_stream2);

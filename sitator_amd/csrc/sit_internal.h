@@ -163,6 +163,7 @@ struct sit_ctx {
     void *spectrum = nullptr;         // tables and buffers of sit_speed_spectrum (spectrum.hip); opaque here
     void *group = nullptr;            // the grouping of sit_group_by_site (group.hip); opaque here
     void *voronoi = nullptr;          // the result of the last sit_voronoi_nodes (voronoi.hip); opaque here
+    void *coordenv = nullptr;         // the result of the last sit_coordination_environments (coordenv.hip); opaque here
     i64 labels_gen = 0;               // counts every write of the resident labels (and every change of their validity): what a grouping is stamped with
 };
 
@@ -534,6 +535,7 @@ void fitfast_free(sit_ctx *c);
 void spectrum_free(sit_ctx *c);
 void group_free(sit_ctx *c);
 void voronoi_free(sit_ctx *c);
+void coordenv_free(sit_ctx *c);
 // group.hip: the recentred working copy of the current grouping for hull.hip (SIT_ERR_INVALID: none, stale, or no step taken)
 struct GroupWork {
     const double *work;               // [N, 3]

@@ -99,6 +99,23 @@ class VoronoiError(Exception):
         super(VoronoiError, self).__init__(text)
 
 
+class CoordinationEnvironmentError(Exception):
+    """``SiteCoordinationEnvironment``: the Voronoi cell of some sites could not be certified.  Attributes: ``sites`` (site
+    indices), ``statuses`` (per site: 1 the search radius would have to grow beyond the plan, 2 a test within its error bound
+    of a threshold or an atom on the site, 3 a capacity of the plan exceeded)."""
+
+    NAMES = VoronoiError.NAMES
+
+    def __init__(self, sites, statuses):
+        self.sites = [int(a) for a in sites]
+        self.statuses = [int(s) for s in statuses]
+        kinds = sorted(set(self.statuses))
+        text = "Coordination environments: %d sites could not be certified: %s." % (
+            len(self.sites), "; ".join("%s: sites %s" % (self.NAMES.get(k, "status %d" % k),
+                                                         [a for a, s in zip(self.sites, self.statuses) if s == k][:16]) for k in kinds))
+        super(CoordinationEnvironmentError, self).__init__(text)
+
+
 class DeviceDomainError(Exception):
     """Internal: a domain error reported by the C-ABI before it is mapped to the classes above."""
 

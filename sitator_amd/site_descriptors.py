@@ -8,6 +8,10 @@
 clustering of the projections and a vote per site, by the definitions of DESIGN.md section 18 (``sit_pca_covariance``,
 ``sit_pca_project``, ``sit_dpc_graph``, ``sit_dpc_assign``) instead of sklearn and pydpc.
 
+``SiteCoordinationEnvironment`` (reference: ``sitator/site_descriptors/SiteCoordinationEnvironment.py``): the coordinating atoms of
+every site and the continuous shape measure of their polyhedron by the definition of DESIGN.md section 19
+(``sit_coordination_environments``) instead of pymatgen's ChemEnv.
+
 ``SiteVolumes`` (reference: ``sitator/site_descriptors/SiteVolumes.py``): the recentring of every site's point cloud runs on
 the GPU for all sites at once (``sit_grouped_recenter_step``); the convex hulls are qhull's on the host (``hulls="host"``, the
 default) or the device's (``hulls="device"``: ``sit_grouped_hull_volumes``, with qhull for the sites it flags)."""
@@ -17,6 +21,7 @@ import time
 import numpy as np
 
 from . import _lib
+from .errors import CoordinationEnvironmentError
 from .misc import resident_trajectory
 from .site_network import SiteNetwork, Structure
 from .site_trajectory import SiteTrajectory
@@ -616,4 +621,96 @@ class SiteTypeAnalysis(object):
         logger.info(("# of sites   " + "{:<8}" * self.n_types).format(*n_sites_of_each_type))
         if np.any(n_sites_of_each_type == 0):
             logger.warning("WARNING: Had site types with no sites; check clustering settings/voting!")
+        return sn
+
+
+class SiteCoordinationEnvironment(object):
+    """Determine site types from local coordination environments.
+
+    The reference moves one site atom through pymatgen's ChemEnv, one structure-environment computation per site.  Here every
+    site is typed on the GPU by the self-contained definition of DESIGN.md section 19: the coordinating atoms are the face
+    neighbours of the site's Voronoi cell among the static lattice (all periodic images) that pass ChemEnv's "simplest"
+    distance and solid-angle cutoffs, and the environment is the library shape of that coordination number with the smallest
+    continuous shape measure (Pinsky & Avnir), minimised over all vertex assignments.  Agreement with a pymatgen installation is
+    not claimed.
+
+    Adds the site attributes ``coordination_environments`` (``"T:4"``, ``"O:6"``, ...; ``"UN:<n>"`` when no library shape of
+    that coordination number lies under ``max_csm``; ``"BAD:0"`` without a coordinating atom), ``site_type_confidences``,
+    ``coordination_numbers`` and - beyond the reference - ``coordination_csm`` (the shape measure of the environment, NaN
+    without one), and sets ``site_types`` and ``vertices`` (static indices, statics-only numbering, ordered by distance; an index
+    repeats when two images of one atom coordinate the site, which only a tiny cell does).
+
+    :param bool guess_ionic_bonds: ``True`` raises ``NotImplementedError``: bond-valence analysis is not carried.  The default
+        is ``False``, where the reference's is ``True``.
+    :param bool full_chemenv_site_types: number the site types by environment symbol (ascending) instead of by coordination
+        number (ascending).  The reference's order is the hash order of a ``set`` and cannot be reproduced.
+    :param float distance_cutoff: distance of a neighbour / smallest distance at most this (ChemEnv: 1.4).
+    :param float angle_cutoff: solid angle of a neighbour's face / largest solid angle at least this (ChemEnv: 0.3).
+    :param float max_csm: a shape is an environment only with a shape measure below this (ChemEnv: 8.0).
+    :param float tolerance: ``tau`` in Angstrom of the certified empty-sphere tests.
+    :param int device: the GPU.
+    """
+
+    def __init__(self, guess_ionic_bonds=False, full_chemenv_site_types=False, distance_cutoff=1.4, angle_cutoff=0.3, max_csm=8.0,
+                 tolerance=1e-6, device=0):
+        if guess_ionic_bonds:
+            raise NotImplementedError("SiteCoordinationEnvironment: bond-valence analysis (guess_ionic_bonds) is not carried")
+        if not tolerance > 0.0:
+            raise ValueError("SiteCoordinationEnvironment: the tolerance must be positive")
+        if not (distance_cutoff >= 1.0 and 0.0 < angle_cutoff <= 1.0 and max_csm > 0.0):
+            raise ValueError("SiteCoordinationEnvironment: distance_cutoff >= 1, 0 < angle_cutoff <= 1 and max_csm > 0 are required")
+        self._full_chemenv_site_types = bool(full_chemenv_site_types)
+        self._distance_cutoff, self._angle_cutoff, self._max_csm = float(distance_cutoff), float(angle_cutoff), float(max_csm)
+        self._tolerance = float(tolerance)
+        self._device = int(device)
+        self.last_info = None
+
+    def run(self, sn):
+        """``sn`` with type information.  Any site whose cell could not be certified raises ``CoordinationEnvironmentError``: a
+        partly typed network is never returned."""
+        assert isinstance(sn, SiteNetwork)
+        if sn.n_sites == 0:
+            logger.warning("Site network had no sites.")
+            return sn
+        static = sn.static_structure
+        positions = np.ascontiguousarray(static.get_positions(), dtype=np.float64)
+        cell = np.asarray(static.cell, dtype=np.float64).reshape(3, 3)
+        ctx = _lib.HipContext(cell, device=self._device)
+        try:
+            res = ctx.coordination_environments(positions, sn.centers, self._tolerance, self._distance_cutoff, self._angle_cutoff,
+                                                self._max_csm)
+        finally:
+            ctx.close()
+        self.last_info = res["info"]
+        bad = np.nonzero(res["status"] != 0)[0]
+        if len(bad):
+            raise CoordinationEnvironmentError(bad, res["status"][bad])
+        near = np.nonzero(res["flags"] & 1)[0]
+        if len(near):
+            logger.warning("%d sites have a neighbour within 1e-9 (relative) of a cutoff: %s" % (len(near), near[:16].tolist()))
+        numbers = res["n"].astype(np.int64)
+        symbols = []
+        for k in range(sn.n_sites):
+            if numbers[k] == 0:
+                symbols.append("BAD:0")
+            elif res["shape"][k] >= 0:
+                symbols.append(_lib.COORDENV_SHAPES[res["shape"][k]])
+            else:
+                symbols.append("UN:%d" % numbers[k])
+        vertices = [[int(i) for i in v] for v in res["vertices"]]
+        assert np.all(numbers == [len(v) for v in vertices])
+        typearr = symbols if self._full_chemenv_site_types else [int(v) for v in numbers]
+        unique_envs = sorted(set(typearr))
+        site_types = np.array([unique_envs.index(t) for t in typearr])
+        n_types = len(unique_envs)
+        logger.info(("Type         " + "{:<8}" * n_types).format(*unique_envs))
+        logger.info(("# of sites   " + "{:<8}" * n_types).format(*np.bincount(site_types)))
+        csm = np.where(res["shape"] >= 0, res["csm_best"], np.nan)
+        sn.site_types = site_types
+        sn.vertices = vertices
+        for name, value in (("coordination_environments", np.array(symbols)), ("site_type_confidences", res["confidence"].copy()),
+                            ("coordination_numbers", numbers), ("coordination_csm", csm)):
+            if sn.has_attribute(name):
+                sn.remove_attribute(name)
+            sn.add_site_attribute(name, value)
         return sn
