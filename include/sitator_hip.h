@@ -70,7 +70,7 @@ const char *sit_last_message(sit_ctx *ctx);
  * frame), out[5] = bytes of a communicator id (sit_comm_unique_id).  Writes min(n, 6) words and returns 6.  A binding
  * checks its own struct declarations against these once, at import (tests/test_abi.py does it for the ctypes stubs of
  * INTEGRATION.md and sitator_amd/_lib.py).  No context, no GPU needed.                                        */
-#define SIT_ABI_VERSION 13
+#define SIT_ABI_VERSION 14
 int sit_abi(int32_t *out, int n);
 /* Device buffers of 1 MB and more (the trajectory, the landmark rows, labels, the fit's arena) are kept by the process
  * when a context lets go of them, up to as much as its contexts have held at once, and handed to the next context that asks for a similar size: a process
@@ -349,6 +349,30 @@ int sit_recenter_resident(sit_ctx *ctx, const double *masses, const double *fact
 int sit_speed_spectrum(sit_ctx *ctx, const double *positions, int64_t F, const int64_t *atoms, int64_t n_sel,
                        const double *freqs, const uint8_t *fmask, int64_t workspace_bytes, double *avg,
                        double *band_power, double *spectrum, double *speeds);
+
+/* MeanSquaredDisplacement: per selected atom, Cartesian axis and lag tau the mean squared displacement
+ * msd(tau) = (1 / (F - tau)) sum_{t < F - tau} (y[t + tau] - y[t])^2 of the series y[t] = x_u[t] - x_u[0].  With
+ * unwrap != 0, x_u is the trajectory unwrapped under the context's cell: a step d = x[t] - x[t-1] crosses
+ * n_a = nearbyint((d . cell^-1)_a) images (0 where that is not finite), the image counts N[t] = -sum_{s<=t} n[s] are exact
+ * int32 sums and x_u[t] = x[t] + N_0 c_0 + N_1 c_1 + N_2 c_2 (x[t] itself, bit for bit, where N[t] = 0); *max_residual is
+ * the largest |(d . cell^-1)_a - n_a| over all finite steps, in [0, 0.5]: the unwrapping is the true one while every true
+ * step stays below half a cell vector.  With unwrap == 0, x_u = x and *max_residual = 0.
+ * positions: host [F, n_sel, 3], or NULL for the frames resident after sit_set_frames, of which `atoms` [n_sel] names the
+ * columns (F must then be the context's).
+ * lags == NULL: all lags 0 .. max_lag (n_lags is taken as max_lag + 1) by msd = S1 - 2 acf / (F - tau), the autocorrelation
+ * through a zero-padded float64 transform of length 2^m >= 2 F - 1 per (atom, axis), S1 from prefix sums of y^2; r4 must be
+ * NULL.  lags != NULL: the n_lags lags listed (each in [0, F - 1], duplicates allowed) by the sums themselves, and
+ * r4 [n_sel, n_lags] (optional) = (1 / (F - tau)) sum_t (|y[t + tau] - y[t]|^2)^2.  Lag 0 is exactly 0.
+ * msd [n_sel, 3, n_lags].  collective != 0: coll [3, n_lags] = the same of Y[t] = sum_i y_i[t] (atoms added in selection
+ * order), divided by n_sel.  images [n_sel, F, 3] (optional, int32): N[t].
+ * workspace_bytes: cap on the device buffers of a batch of atoms (0: SITATOR_SPECTRUM_WORKSPACE_MB, default 1024); an
+ * atom's results do not depend on the batch or on the other atoms.  Reads only: frames, rows, labels and their validity
+ * stay as they are.  SIT_ERR_INVALID: F < 2 or > 2^29, a lag or max_lag outside [0, F - 1], r4 without lags, coll without
+ * collective or the reverse, an atom outside [0, A), F other than the resident frames', a cap below one atom's buffers, a
+ * degenerate cell with unwrap.                                                                             */
+int sit_msd(sit_ctx *ctx, const double *positions, int64_t F, const int64_t *atoms, int64_t n_sel, int unwrap,
+            int64_t max_lag, const int64_t *lags, int64_t n_lags, int collective, int64_t workspace_bytes, double *msd,
+            double *r4, double *coll, int32_t *images, double *max_residual);
 
 /* GenerateClampedTrajectory (misc/GenerateClampedTrajectory.pyx:92-126): out[F, A, 3] (host) holds for every frame and
  * atom, by role[a]: -1 the atom's real position, -2 fixed_pos[a], m >= 0 the centre of the site that column m of the

@@ -15,6 +15,7 @@ from .dotprod_classifier import DotProdClassifier, LandmarkVectors  # noqa: F401
 from .landmark import LandmarkAnalysis  # noqa: F401
 from .dynamics import (AverageVibrationalFrequency, GenerateClampedTrajectory, JumpAnalysis, MergeSitesByDynamics,  # noqa: F401
                        MergeSitesByThreshold, RemoveUnoccupiedSites, ReplaceUnassignedPositions, SmoothSiteTrajectory)
+from .dynamics import MeanSquaredDisplacement, MSDResult, diffusion_coefficient  # noqa: F401
 from .merging import MergeSites, MergeSitesError, MergedSitesTooDistantError  # noqa: F401
 from .recenter import RecenterTrajectory  # noqa: F401
 from .misc import GenerateAroundSites, NAvgsPerSite  # noqa: F401

@@ -40,7 +40,7 @@ class FillParams(C.Structure):
                    int(store_rows), int(assign), int(predict_normed), int(defer), float(predict_threshold))
 
 
-ABI_VERSION = 13       # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
+ABI_VERSION = 14       # SIT_ABI_VERSION of include/sitator_hip.h this table was written against
 
 
 # every symbol include/sitator_hip.h declares: (restype, argtypes)
@@ -102,6 +102,7 @@ SIGNATURES = {
     "sit_recenter_resident": (C.c_int, [_vp, _dp, _dp, _dp]),
     "sit_recenter": (C.c_int, [_vp, _dp, i64, i64, _dp, _dp, _dp]),
     "sit_speed_spectrum": (C.c_int, [_vp, _dp, i64, _ip, i64, _dp, _u8p, i64, _dp, _dp, _dp, _dp]),
+    "sit_msd": (C.c_int, [_vp, _dp, i64, _ip, i64, C.c_int, i64, _ip, i64, C.c_int, i64, _dp, _dp, _dp, _i32p, _dp]),
     "sit_clamp_trajectory": (C.c_int, [_vp, _dp, i64, i64, _i32p, _dp, _dp, i64, C.c_int, C.c_int, i64, _dp, _ip]),
     "sit_group_by_site": (C.c_int, [_vp, _dp, i64, i64, _ip, i64, i64, i64, _ip]),
     "sit_grouped_fetch": (C.c_int, [_vp, i64, i64, _dp, _dp, _ip]),
@@ -851,6 +852,46 @@ class HipContext(object):
             _d(freqs), fmask.ctypes.data_as(_u8p), int(workspace_bytes), _d(avg), _d(power),
             None if spec is None else spec.ctypes.data_as(_dp), None if spd is None else _d(spd)))
         return avg, power, spec, spd
+
+    # -- MeanSquaredDisplacement: reads frames only (labels_version, rows and labels stay)
+    def msd(self, positions=None, atoms=None, unwrap=True, max_lag=None, lags=None, collective=False, workspace_bytes=0,
+            r4=False, images=False):
+        """``(msd [n_sel, 3, n_lags], r4 [n_sel, n_lags], coll [3, n_lags], images int32 [n_sel, F, 3], max_residual)`` of
+        ``sit_msd``; whatever was not asked for is ``None``.  ``positions``: a host ``[F, n_sel, 3]`` float64 array; without
+        it ``atoms`` names columns of the frames resident after ``set_frames``.  ``lags=None``: all lags ``0 .. max_lag``
+        (``None``: ``F // 2``) through the transform; otherwise the lags listed, by direct sums, with ``r4`` on request.
+        ``unwrap``: under the context's cell.  ``workspace_bytes``: cap on the device buffers of a batch of atoms (0: the
+        default of 1 GiB).  A lag or an atom out of range, and any other argument that does not fit, raises
+        ``ValueError``."""
+        if positions is not None:
+            positions = _f64(positions)
+            assert positions.ndim == 3 and positions.shape[2] == 3
+            F, n_sel = positions.shape[0], positions.shape[1]
+            idx = None
+        else:
+            idx = _i64(atoms).reshape(-1)
+            F, n_sel = self.F, len(idx)
+        if lags is None:
+            lag_arr = None
+            max_lag = F // 2 if max_lag is None else int(max_lag)
+            n_lags = max(max_lag, 0) + 1
+            if r4:
+                raise ValueError("msd: the fourth moment comes with an explicit lag list only")
+        else:
+            lag_arr = _i64(lags).reshape(-1)
+            max_lag, n_lags = 0, len(lag_arr)
+        out = np.zeros((n_sel, 3, n_lags))
+        out4 = np.zeros((n_sel, n_lags)) if r4 else None
+        coll = np.zeros((3, n_lags)) if collective else None
+        img = np.zeros((n_sel, max(F, 0), 3), dtype=np.int32) if images else None
+        res = C.c_double(0.0)
+        rc = self.lib.sit_msd(
+            self._h, None if positions is None else _d(positions), int(F), None if idx is None else _i(idx), int(n_sel),
+            int(bool(unwrap)), int(max_lag), None if lag_arr is None else _i(lag_arr), int(n_lags), int(bool(collective)),
+            int(workspace_bytes), _d(out), None if out4 is None else _d(out4), None if coll is None else _d(coll),
+            None if img is None else img.ctypes.data_as(_i32p), C.byref(res))
+        self._check(rc)
+        return out, out4, coll, img, res.value
 
     # -- GenerateClampedTrajectory: reads labels and frames only (labels_version, rows and labels stay)
     def clamp_trajectory(self, role, fixed_pos, centers, wrap, pass_through_unassigned, positions=None, workspace_bytes=0):

@@ -15,6 +15,8 @@
 //   load   plain | speeds x chirp with the zero padding (first forward pass) | conj twiddle (inverse passes)
 //   middle forward | inverse | forward, x B, inverse (the last level: its lines are transformed there and back in one go)
 //   store  plain | twiddle (forward passes) | x w_k / M, re^2 + im^2, the band sums (last inverse pass)
+// and, for the autocorrelation of a real series (msd.hip; the existing values keep their numbers and their code):
+//   load   a real series with the zero padding | middle forward, re^2 + im^2, inverse | store S1 - 2 re / (M (F - lag))
 // M <= 2^10: one launch per batch of atoms; M <= 2^20: three; M <= 2^30: five.  Every atom's transform is its own - an
 // atom's arithmetic does not depend on which atoms share a launch - and the band sums are reduced in a fixed order:
 // per thread in index order, a tree over the workgroup, the workgroups of an atom one after the other.
@@ -23,25 +25,7 @@
 
 #include "sit_internal.h"
 #include "spectrum_plan.h"
-
-enum { SP_LOAD_PLAIN = 0, SP_LOAD_FIRST = 1, SP_LOAD_UNTWIDDLE = 2 };
-enum { SP_MID_FWD = 1, SP_MID_INV = 2, SP_MID_CONV = 3 };
-enum { SP_STORE_PLAIN = 0, SP_STORE_TWIDDLE = 1, SP_STORE_BAND = 2 };
-
-struct SpArgs {
-    double2 *buf;                  // [atoms of the batch][M], transformed in place
-    const double *speeds;          // [atoms of the batch][n]
-    const double2 *chirp;          // [n]   w_j
-    const double2 *root;           // [M]   exp(-2 pi i e / M)
-    const double2 *filter;         // [M]   B, in the order the forward passes leave
-    const double *freqs;           // [nbins]
-    const unsigned char *fmask;    // [nbins]
-    double *partial;               // [atoms of the batch][tiles][2]
-    double2 *spec;                 // [atoms of the batch][nbins] or null
-    i64 n, M, nbins, L, S, tiles;
-    int bits, log_s, lines, log_lines, pad, load, mid, store;
-    double inv_m;
-};
+#include "msd_plan.h"
 
 // speeds[c][t] = |x[t+1][atom_c] - x[t][atom_c]| for the atoms [a0, a0 + nb) of the selection, in the reference's
 // operation order (a plain difference, sqrt((dx^2 + dy^2) + dz^2)).  A 32 x 32 tile: read with the atoms across lanes
@@ -97,6 +81,8 @@ __global__ __launch_bounds__(SP_THREADS) void k_spec_pass(SpArgs a)
                 const double2 c = a.chirp[g];
                 xr = sp * c.x; xi = sp * c.y;
             }
+        } else if (a.load == SP_LOAD_REAL) {                                // a real series, zero-padded to M
+            if (g < a.n) xr = a.speeds[atom * a.n + g];
         } else {
             const double2 v = buf[g];
             xr = v.x; xi = v.y;
@@ -137,6 +123,16 @@ __global__ __launch_bounds__(SP_THREADS) void k_spec_pass(SpArgs a)
         }
         __syncthreads();
     }
+    if (a.mid == SP_MID_POWER) {                                             // |X|^2: the transform of the autocorrelation
+        for (i64 idx = tid; idx < points; idx += SP_THREADS) {
+            int t; i64 l;
+            if (tfast) { t = (int)(idx & (T - 1)); l = idx >> a.log_lines; } else { l = idx & (L - 1); t = (int)(idx >> bits); }
+            const i64 o = t * LP + l;
+            const double xr = re[o], xi = im[o];
+            re[o] = xr * xr + xi * xi; im[o] = 0.0;
+        }
+        __syncthreads();
+    }
     if (a.mid & SP_MID_INV) {
         for (int st = 0; st < bits; st++) {                                  // the inverse of every stage above, last one first
             const i64 h = (i64)1 << st;
@@ -171,6 +167,9 @@ __global__ __launch_bounds__(SP_THREADS) void k_spec_pass(SpArgs a)
                     num += a.freqs[g] * pw; den += pw;
                 }
             }
+        } else if (a.store == SP_STORE_MSD) {
+            // the first level: g is the lag.  `re` is M times the autocorrelation of the series (msd_plan.h)
+            if (g < a.nbins) a.msd[atom * a.nbins + g] = msd_combine(msd_s1(a.psum + atom * (a.n + 1), a.n, g), xr, a.inv_m, a.n, g);
         } else {
             if (a.store == SP_STORE_TWIDDLE && a.S > 1) {                    // x W_{L S}^{s k}, k = bitrev(l)
                 const double2 w = a.root[s * sp_bitrev(l, bits) * tw_step];
@@ -212,6 +211,9 @@ struct SpState {
     i64 n = 0;                                  // the length the tables were made for (0: none)
     double2 *chirp = nullptr, *root = nullptr, *filter = nullptr;
     i64 chirp_cap = 0, root_cap = 0, filter_cap = 0;
+    i64 roots_m = 0;                            // sp_roots: the M its table was made for (0: none)
+    double2 *roots = nullptr;
+    i64 roots_cap = 0;
     void *work = nullptr, *aux = nullptr, *pos = nullptr;
     i64 work_cap = 0, aux_cap = 0, pos_cap = 0;
 };
@@ -229,7 +231,7 @@ void spectrum_free(sit_ctx *c)
 {
     SpState *st = (SpState *)c->spectrum;
     if (!st) return;
-    void *ptrs[] = {st->chirp, st->root, st->filter, st->work, st->aux, st->pos};
+    void *ptrs[] = {st->chirp, st->root, st->filter, st->roots, st->work, st->aux, st->pos};
     for (void *p : ptrs) if (p) sit_dfree(c, p);
     delete st;
     c->spectrum = nullptr;
@@ -237,7 +239,7 @@ void spectrum_free(sit_ctx *c)
 
 static int sp_log2(i64 v) { int b = 0; while (((i64)1 << b) < v) b++; return b; }
 
-static int sp_launch(sit_ctx *c, const SpPlan &pl, int level, SpArgs a, int load, int mid, int store, i64 nb)
+int sp_launch(sit_ctx *c, const SpPlan &pl, int level, SpArgs a, int load, int mid, int store, i64 nb)
 {
     const SpPass &q = pl.pass[level];
     a.L = q.L; a.S = q.S; a.bits = q.bits; a.log_s = sp_log2(q.S); a.lines = q.lines; a.log_lines = sp_log2(q.lines);
@@ -245,6 +247,37 @@ static int sp_launch(sit_ctx *c, const SpPlan &pl, int level, SpArgs a, int load
     HIP_TRY(c, lds_limit((const void *)k_spec_pass, q.lds, c->device));
     k_spec_pass<<<dim3((unsigned)q.tiles, (unsigned)nb), dim3(SP_THREADS), q.lds, c->stream>>>(a);
     HIP_TRY(c, hipGetLastError());
+    return SIT_OK;
+}
+
+// tab[e] = exp(-2 pi i e / M), M = tab.size(), in extended precision and rounded once
+static void sp_root_values(std::vector<double2> &tab)
+{
+    const long double pi = 3.141592653589793238462643383279502884L;
+    const i64 M = (i64)tab.size();
+    for (i64 e = 0; e < M; e++) {
+        const long double ph = 2.0L * pi * ((long double)e / (long double)M);
+        tab[(size_t)e] = make_double2((double)cosl(ph), (double)-sinl(ph));
+    }
+}
+
+// The M-th roots of unity alone, for a transform that needs neither chirp nor filter (msd.hip): made as sp_tables makes
+// them, kept with the context until another M is asked for.
+int sp_roots(sit_ctx *c, i64 M, const double2 **root)
+{
+    if (!c->spectrum) c->spectrum = new SpState();
+    SpState *st = (SpState *)c->spectrum;
+    if (st->roots_m != M) {
+        st->roots_m = 0;
+        int rc;
+        if ((rc = sp_grow(c, (void **)&st->roots, &st->roots_cap, M * 16))) return rc;
+        std::vector<double2> tab((size_t)M);
+        sp_root_values(tab);
+        HIP_TRY(c, hipMemcpyAsync(st->roots, tab.data(), (size_t)M * 16, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        st->roots_m = M;
+    }
+    *root = st->roots;
     return SIT_OK;
 }
 
@@ -268,10 +301,7 @@ static int sp_tables(sit_ctx *c, SpState *st, const SpPlan &pl, i64 n)
         chirp[(size_t)j] = make_double2((double)cosl(ph), (double)-sinl(ph));
     }
     HIP_TRY(c, hipMemcpyAsync(st->chirp, chirp.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    for (i64 e = 0; e < M; e++) {
-        const long double ph = 2.0L * pi * ((long double)e / (long double)M);
-        tab[(size_t)e] = make_double2((double)cosl(ph), (double)-sinl(ph));
-    }
+    sp_root_values(tab);
     HIP_TRY(c, hipMemcpyAsync(st->root, tab.data(), (size_t)M * 16, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));                             // tab is reused
     for (i64 e = 0; e < M; e++) tab[(size_t)e] = make_double2(0.0, 0.0);

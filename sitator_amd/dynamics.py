@@ -16,6 +16,9 @@ device-resident site assignments:
   ``LandmarkAnalysis`` left resident)
 * ``GenerateClampedTrajectory``  (reference ``sitator/misc/GenerateClampedTrajectory.pyx:13-128``; one pass of the device
   over the resident labels and the frames, also straight from the trajectory a ``LandmarkAnalysis`` left resident)
+* ``MeanSquaredDisplacement`` and ``diffusion_coefficient``  (no counterpart in the reference; the tracer and the collective
+  mean squared displacement against the lag, unwrapped under the cell on the device, also straight from the trajectory a
+  ``LandmarkAnalysis`` left resident)
 """
 import logging
 import operator
@@ -742,3 +745,143 @@ class GenerateClampedTrajectory(object):
         if len(role) != ctx.A:
             raise ValueError("The structure has %d atoms, the resident frames %d" % (len(role), ctx.A))
         return self._call(ctx, sn, role, None, True)
+
+
+class MSDResult(object):
+    """What ``MeanSquaredDisplacement`` returns.
+
+    ``lags`` int64 ``[n_lags]`` (frames); ``msd_axes`` ``[n_sel, n_lags, 3]`` per atom and Cartesian axis; ``msd``
+    ``[n_sel, n_lags]`` their sum over the axes; ``mean`` ``[n_lags]`` its mean over the atoms (the tracer MSD);
+    ``collective`` ``[n_lags, 3]`` (the MSD of the summed displacement divided by the number of atoms: its ratio to the
+    tracer MSD is the Haven ratio) or ``None``; ``alpha2`` ``[n_sel, n_lags]`` the non-Gaussian parameter
+    ``3 <r^4> / (5 <r^2>^2) - 1`` (explicit lags only, else ``None``; NaN at lag 0); ``max_residual`` the largest distance
+    of a step from a whole number of cell vectors, in units of them; ``images`` int32 ``[n_sel, n_frames, 3]`` the image
+    counts of the unwrapping (only when asked for, else ``None``)."""
+
+    def __init__(self, lags, msd_axes, collective, r4, max_residual, images):
+        self.lags = lags
+        self.msd_axes = msd_axes
+        self.msd = (msd_axes[..., 0] + msd_axes[..., 1]) + msd_axes[..., 2]
+        self.mean = np.mean(self.msd, axis=0) if len(self.msd) else np.full(len(lags), np.nan)
+        self.collective = collective
+        self.r4 = r4
+        if r4 is None:
+            self.alpha2 = None
+        else:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                self.alpha2 = 3.0 * r4 / (5.0 * self.msd * self.msd) - 1.0
+        self.max_residual = max_residual
+        self.images = images
+
+
+def diffusion_coefficient(lags, msd, timestep=1.0, fit_range=None, dimensions=3):
+    """``(D, intercept)``: ordinary least squares of ``msd`` on ``lags * timestep`` with an intercept,
+    ``D = slope / (2 * dimensions)`` (Einstein's relation).  ``fit_range``: ``(first, last)`` lag, inclusive, in frames;
+    ``None``: every lag given.  Host numpy."""
+    lags = np.asarray(lags, dtype=np.float64)
+    msd = np.asarray(msd, dtype=np.float64)
+    if lags.shape != msd.shape or lags.ndim != 1:
+        raise ValueError("lags and msd must be one-dimensional and of one length")
+    if fit_range is not None:
+        keep = (lags >= fit_range[0]) & (lags <= fit_range[1])
+        lags, msd = lags[keep], msd[keep]
+    if len(lags) < 2:
+        raise ValueError("A fit needs at least two lags")
+    t = lags * timestep
+    tm, mm = np.mean(t), np.mean(msd)
+    slope = np.sum((t - tm) * (msd - mm)) / np.sum((t - tm) * (t - tm))
+    return slope / (2 * dimensions), mm - slope * tm
+
+
+class MeanSquaredDisplacement(object):
+    """Mean squared displacement of chosen atoms against the lag time, per atom and Cartesian axis: the tracer MSD, from
+    which ``diffusion_coefficient`` fits D, and with ``collective`` the MSD of the summed displacement (the "charge" MSD;
+    its ratio to the tracer one is the Haven ratio).  The reference has no such operator; the definitions are in
+    ``DESIGN.md`` section 20.
+
+    ``max_lag``: all lags ``0 .. max_lag`` (``None``: ``n_frames // 2``), by the autocorrelation of every unwrapped series
+    through a zero-padded float64 transform and a windowed sum (``sit_msd``: O(F log F) per atom and axis).  ``lags``:
+    instead, the lags listed (log-spaced ones, say), by the sums themselves, one workgroup per (lag, atom); this path also
+    gives the non-Gaussian parameter ``alpha2``.  ``unwrap``: the trajectory is unwrapped under the cell first - a step is
+    taken to cross the whole number of cell vectors nearest to it, which is right for any cell shape while no atom moves
+    half a cell vector or more between two frames; ``MSDResult.max_residual`` says how close the trajectory came, and a
+    value above 0.25 logs a warning.  A trajectory that is unwrapped already passes through bit for bit.
+
+    The site-hop MSD (displacements counted from site centre to site centre) is this operator applied to the output of
+    ``GenerateClampedTrajectory(wrap=False)``."""
+
+    def __init__(self, max_lag=None, lags=None, unwrap=True, collective=False):
+        if max_lag is not None and lags is not None:
+            raise ValueError("Give max_lag or lags, not both")
+        self.max_lag = max_lag
+        self.lags = None if lags is None else np.array(lags, dtype=np.int64).reshape(-1)
+        self.unwrap = unwrap
+        self.collective = collective
+
+    def _result(self, n_frames, raw):
+        msd, r4, coll, images, max_residual = raw
+        lags = self.lags if self.lags is not None else np.arange(msd.shape[2], dtype=np.int64)
+        if max_residual > 0.25:
+            logger.warning("MeanSquaredDisplacement: a step of %.3f cell vectors from the nearest whole number of them - a "
+                           "step of a quarter of the cell is not molecular dynamics; the unwrapping may be wrong."
+                           % max_residual)
+        return MSDResult(lags, np.ascontiguousarray(msd.transpose(0, 2, 1)), None if coll is None else np.ascontiguousarray(coll.T),
+                         r4, max_residual, images)
+
+    def _empty(self, n_frames, images):
+        if n_frames < 2:
+            raise ValueError("A trajectory of %d frames has no displacements" % n_frames)
+        n_lags = len(self.lags) if self.lags is not None else (n_frames // 2 if self.max_lag is None else self.max_lag) + 1
+        raw = (np.zeros((0, 3, n_lags)), np.zeros((0, n_lags)) if self.lags is not None else None,
+               np.full((3, n_lags), np.nan) if self.collective else None,
+               np.zeros((0, n_frames, 3), dtype=np.int32) if images else None, 0.0)
+        return self._result(n_frames, raw)
+
+    def _call(self, ctx, images, **kw):
+        return ctx.msd(unwrap=self.unwrap, max_lag=self.max_lag, lags=self.lags, collective=self.collective,
+                       r4=self.lags is not None, images=images, **kw)
+
+    def compute(self, traj, cell, mask, images=False):
+        """``traj``: a host trajectory ``[n_frames, n_atoms, 3]``, float64, not modified; ``cell``: rows are the cell
+        vectors (looked at only with ``unwrap``); ``mask``: the atoms, a boolean mask or an index array (whatever
+        ``traj[:, mask]`` takes).  Returns an ``MSDResult``.  ``ValueError`` for fewer than two frames, another dtype, a lag
+        beyond ``n_frames - 1`` or a degenerate cell."""
+        traj = np.asarray(traj)
+        if traj.ndim != 3 or traj.shape[2] != 3:
+            raise ValueError("Wrong shape %s for traj." % (traj.shape,))
+        if traj.dtype != np.float64:
+            raise ValueError("Buffer dtype mismatch, expected 'double' but got '%s'" % traj.dtype)
+        selected = np.ascontiguousarray(traj[:, mask])             # a copy: the caller's array stays as it is
+        if selected.ndim != 3:
+            raise ValueError("`mask` must select along the atoms")
+        if selected.shape[1] == 0:
+            return self._empty(traj.shape[0], images)
+        ctx = _lib.HipContext(np.asarray(cell, dtype=np.float64) if self.unwrap else np.eye(3))
+        try:
+            raw = self._call(ctx, images, positions=selected)
+        finally:
+            ctx.close()
+        return self._result(traj.shape[0], raw)
+
+    def compute_for_analysis(self, la, mask=None, images=False):
+        """The same from the trajectory a ``LandmarkAnalysis`` that has run left on its GPU, under that analysis' cell: no
+        upload, no gather on the host.  ``mask``: boolean mask or index array over the atoms of a frame; ``None``: the
+        mobile atoms of the run.
+
+        The frames are those ``run()`` received, as they were at that time.  Frames the analysis recentred on the device
+        (``recenter_masses``) are accepted: they are the trajectory relative to the framework's centre of mass, and an MSD
+        relative to the framework is what one wants from a cell that drifts.  ``NotImplementedError`` after a run over
+        frame shards (``comm`` of more than one rank, ``devices=[...]`` of more than one GPU): a lag reaches across the
+        shards."""
+        la._need_run()
+        if getattr(la, "_children", None) is not None or la._comm.size > 1 or la._ctx is None:
+            raise NotImplementedError("MeanSquaredDisplacement needs all frames of the trajectory on one GPU; "
+                                      "this analysis ran over frame shards")
+        ctx = la._ctx
+        if mask is None:
+            atoms = np.asarray(la._mobile_idx, dtype=np.int64)
+        else:
+            atoms = np.arange(ctx.A, dtype=np.int64)[mask]         # numpy's rules: length, negative indices, bounds
+        if len(atoms) == 0:
+            return self._empty(ctx.F, images)
+        return self._result(ctx.F, self._call(ctx, images, atoms=atoms))
