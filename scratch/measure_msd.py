@@ -1,5 +1,6 @@
 """One warm call of MeanSquaredDisplacement.compute_for_analysis at the benchmark's C2 size (100 000 frames, 64 mobile ions): all
-lags to F // 2 and 64 log-spaced direct lags, beside the numpy restatement of the all-lag path on this machine's CPUs."""
+lags to F // 2, 64 log-spaced direct lags, and the same call of AverageVibrationalFrequency, beside the numpy restatement of
+the all-lag path on this machine's CPUs (SITATOR_LIB: another build of the library, for A/B runs in turns)."""
 import json
 import os
 import sys
@@ -9,7 +10,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from sitator_amd import LandmarkAnalysis, MeanSquaredDisplacement, SiteNetwork, Structure, synth  # noqa: E402
+from sitator_amd import AverageVibrationalFrequency, LandmarkAnalysis, MeanSquaredDisplacement, SiteNetwork, Structure, synth  # noqa: E402
 from tests import msd_ref as R  # noqa: E402
 
 F, cfg = 100000, "C2"
@@ -49,6 +50,9 @@ for name, op in [("all_lags", MeanSquaredDisplacement()), ("all_lags_collective"
     if name.startswith("direct"):
         direct = res
 
+avg, ts = timed(lambda: AverageVibrationalFrequency().compute_for_analysis(la))
+out["speed_spectrum"] = {"seconds": [round(t, 5) for t in ts], "min": min(ts), "median": float(np.median(ts)), "avg_frequency": float(avg)}
+print("speed_spectrum", out["speed_spectrum"], flush=True)
 # the two device paths against each other at the direct lags, in the units of the all-lag bound
 sel = np.ascontiguousarray(frames[:, gen.mobile_mask])
 y = R.series(sel, np.asarray(host.cell, dtype=np.float64))
@@ -79,5 +83,4 @@ emu = np.array(emu).transpose(0, 2, 1)
 out["numpy"] = {"gather_unwrap_series_seconds": t_series, "fft_one_thread_seconds_extrapolated": t_one, "fft_16_threads_seconds": t_16}
 out["device_vs_numpy_in_units_of_sum_y2"] = float(np.max(np.abs(emu - dev.msd_axes) * (F - np.arange(n_lags))[None, :, None] / unit[:, None, :]))
 print(out["numpy"], out["device_vs_numpy_in_units_of_sum_y2"], flush=True)
-dest = sys.argv[1] if len(sys.argv) > 1 else "msd_bench.json"
-json.dump(out, open(dest, "w"), indent=1)
+json.dump(out, open(sys.argv[1] if len(sys.argv) > 1 else "msd_bench.json", "w"), indent=1)

@@ -823,6 +823,15 @@ class HipContext(object):
         a3 = None if add3 is None else _f64(add3)
         self._check(self.lib.sit_recenter_resident(self._h, _d(masses), _d(factors), None if a3 is None else _d(a3)))
 
+    def _selection(self, positions, atoms):
+        """``(positions, idx, F, n_sel)``: a host ``[F, n_sel, 3]`` array, or ``atoms`` as columns of the resident frames."""
+        if positions is not None:
+            positions = _f64(positions)
+            assert positions.ndim == 3 and positions.shape[2] == 3
+            return positions, None, positions.shape[0], positions.shape[1]
+        idx = _i64(atoms).reshape(-1)
+        return None, idx, self.F, len(idx)
+
     # -- AverageVibrationalFrequency: reads frames only (labels_version, rows and labels stay)
     def speed_spectrum(self, freqs, fmask, positions=None, atoms=None, workspace_bytes=0, spectrum=False, speeds=False):
         """Per selected atom ``(avg, band_power, spectrum, speeds)`` of the speeds ``|x[t+1] - x[t]|`` (``sit_speed_spectrum``):
@@ -831,14 +840,7 @@ class HipContext(object):
         ``n = F - 1``.  ``positions``: a host ``[F, n_sel, 3]`` float64 array; without it ``atoms`` names columns of the
         frames resident after ``set_frames``.  ``workspace_bytes``: cap on the device buffers of a batch of atoms (0: the
         default of 1 GiB)."""
-        if positions is not None:
-            positions = _f64(positions)
-            assert positions.ndim == 3 and positions.shape[2] == 3
-            F, n_sel = positions.shape[0], positions.shape[1]
-            idx = None
-        else:
-            idx = _i64(atoms).reshape(-1)
-            F, n_sel = self.F, len(idx)
+        positions, idx, F, n_sel = self._selection(positions, atoms)
         nbins = max(F - 1, 0) // 2 + 1
         freqs = _f64(freqs)
         fmask = np.ascontiguousarray(fmask, dtype=np.uint8)
@@ -863,14 +865,7 @@ class HipContext(object):
         ``unwrap``: under the context's cell.  ``workspace_bytes``: cap on the device buffers of a batch of atoms (0: the
         default of 1 GiB).  A lag or an atom out of range, and any other argument that does not fit, raises
         ``ValueError``."""
-        if positions is not None:
-            positions = _f64(positions)
-            assert positions.ndim == 3 and positions.shape[2] == 3
-            F, n_sel = positions.shape[0], positions.shape[1]
-            idx = None
-        else:
-            idx = _i64(atoms).reshape(-1)
-            F, n_sel = self.F, len(idx)
+        positions, idx, F, n_sel = self._selection(positions, atoms)
         if lags is None:
             lag_arr = None
             max_lag = F // 2 if max_lag is None else int(max_lag)

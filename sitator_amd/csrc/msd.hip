@@ -1,6 +1,8 @@
 // MeanSquaredDisplacement: the tracer and the collective mean squared displacement of chosen atoms against the lag, per
 // Cartesian axis, from the frames as they lie in device memory.  Every decision - the image of a step, the operation
-// order of an unwrapped position, the chunks and the order of the scans, S1, the combination - is in msd_plan.h.
+// order of an unwrapped position, the chunks and the order of the scans, S1, the combination, the pieces of a call's buffer
+// (msd_layout) - is in msd_plan.h.  Where the selected atoms come from and the tile that k_msd_shift and k_msd_series read
+// them through are in series.h, shared with spectrum.hip.
 //
 //   k_msd_shift      the image shift of every step and the largest distance of a step from a whole image
 //   k_msd_scan_*     sums along the frames in chunks: the totals of the chunks, their exclusive sums, the apply pass
@@ -15,45 +17,33 @@
 #include <cstdio>
 #include <cstring>
 
-#include "sit_internal.h"
+#include "series.h"
+#include "spectrum_pass.h"
 #include "msd_plan.h"
 
 struct MsdCell { double cm[9], ci[9]; };
 
-// shift[c][a][t] = -image of the step t-1 -> t of atom c along cell vector a (0 at t = 0).  A 32 x 32 tile: read with the
-// atoms across lanes (neighbours in a frame), written with the frames across lanes (the scans read a series as one run).
-__global__ __launch_bounds__(256) void k_msd_shift(const double *pos, i64 A, const i64 *atoms, i64 a0, i64 nb, i64 F, MsdCell cell,
-                                                   i32 *shift, u64 *max_residual_bits)
+// shift[c][a][t] = -image of the step t-1 -> t of atom c along cell vector a (0 at t = 0), through the tile of series.h
+// (the scans read a series as one run), and behind it the largest residual of the steps the workgroup looked at.
+__global__ __launch_bounds__(256) void k_msd_shift(SeriesSource src, i64 a0, i64 nb, i64 F, MsdCell cell, i32 *shift, u64 *max_residual_bits)
 {
-    __shared__ i32 tile[3][32][33];
     __shared__ double red[256];
-    const i64 t0 = (i64)blockIdx.x * 32, c0 = (i64)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     double worst = 0.0;
-    for (int r = ty; r < 32; r += 8) {
-        const i64 t = t0 + r, c = c0 + tx;
-        if (t < F && c < nb) {
-            i32 n[3] = {0, 0, 0};
-            if (t > 0) {
-                const i64 atom = atoms ? atoms[a0 + c] : a0 + c;
-                const double *p1 = pos + (t * A + atom) * 3, *p0 = p1 - A * 3;
-                const double dx = p1[0] - p0[0], dy = p1[1] - p0[1], dz = p1[2] - p0[2];
-                for (int a = 0; a < 3; a++) {
-                    double res;
-                    n[a] = -msd_image(msd_frac(cell.ci, a, dx, dy, dz), &res);
-                    if (res > worst) worst = res;
-                }
+    series_tile<3, i32>(a0, nb, F,
+        [&](i64 t, i64 column, i32 *n) {
+            n[0] = n[1] = n[2] = 0;
+            if (t == 0) return;
+            const double *p1 = src.at(t, column), *p0 = p1 - src.A * 3;
+            const double dx = p1[0] - p0[0], dy = p1[1] - p0[1], dz = p1[2] - p0[2];
+            for (int a = 0; a < 3; a++) {
+                double res;
+                n[a] = -msd_image(msd_frac(cell.ci, a, dx, dy, dz), &res);
+                if (res > worst) worst = res;
             }
-            tile[0][r][tx] = n[0]; tile[1][r][tx] = n[1]; tile[2][r][tx] = n[2];
-        }
-    }
+        },
+        [&](i64 t, i64 c, const i32 *n) { for (int a = 0; a < 3; a++) shift[(c * 3 + a) * F + t] = n[a]; });
     red[threadIdx.x] = worst;
     __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const i64 c = c0 + r, t = t0 + tx;
-        if (t < F && c < nb)
-            for (int a = 0; a < 3; a++) shift[(c * 3 + a) * F + t] = tile[a][tx][r];
-    }
     for (int s = 128; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s && red[threadIdx.x + s] > red[threadIdx.x]) red[threadIdx.x] = red[threadIdx.x + s];
         __syncthreads();
@@ -140,33 +130,23 @@ template <typename T> __global__ void k_msd_zero_first(T *P, i64 stride, i64 n_s
     if (s < n_series) P[s * stride] = (T)0;
 }
 
-// y[c][a][t] = x_u[t] - x_u[0] (images: null with unwrap off); the tile of k_msd_shift, three coordinates deep
-__global__ __launch_bounds__(256) void k_msd_series(const double *pos, i64 A, const i64 *atoms, i64 a0, i64 nb, i64 F, MsdCell cell,
-                                                    const i32 *images, double *y)
+// y[c][a][t] = x_u[t] - x_u[0] (images: null with unwrap off); the same tile, three coordinates deep.  `first`: x[0] of
+// the tile's 32 columns, left by whoever loads the tile's first frame.
+__global__ __launch_bounds__(256) void k_msd_series(SeriesSource src, i64 a0, i64 nb, i64 F, MsdCell cell, const i32 *images, double *y)
 {
-    __shared__ double tile[3][32][33];
     __shared__ double first[3][32];
-    const i64 t0 = (i64)blockIdx.x * 32, c0 = (i64)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int r = ty; r < 32; r += 8) {
-        const i64 t = t0 + r, c = c0 + tx;
-        if (t < F && c < nb) {
-            const i64 atom = atoms ? atoms[a0 + c] : a0 + c;
-            const double *p = pos + (t * A + atom) * 3;
-            tile[0][r][tx] = p[0]; tile[1][r][tx] = p[1]; tile[2][r][tx] = p[2];
-            if (r == 0) { const double *q = pos + atom * 3; first[0][tx] = q[0]; first[1][tx] = q[1]; first[2][tx] = q[2]; }
-        }
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const i64 c = c0 + r, t = t0 + tx;
-        if (t < F && c < nb) {
+    series_tile<3, double>(a0, nb, F,
+        [&](i64 t, i64 column, double *x) {
+            const double *p = src.at(t, column);
+            x[0] = p[0]; x[1] = p[1]; x[2] = p[2];
+            if (t == (i64)blockIdx.x * 32) { const double *q = src.at(0, column); for (int a = 0; a < 3; a++) first[a][threadIdx.x & 31] = q[a]; }
+        },
+        [&](i64 t, i64 c, const double *x) {
             i32 n0 = 0, n1 = 0, n2 = 0;
             if (images) { n0 = images[(c * 3) * F + t]; n1 = images[(c * 3 + 1) * F + t]; n2 = images[(c * 3 + 2) * F + t]; }
             for (int a = 0; a < 3; a++)                                      // N[0] = 0: x_u[0] is x[0]
-                y[(c * 3 + a) * F + t] = msd_unwrap(tile[a][tx][r], n0, n1, n2, cell.cm, a) - first[a][r];
-        }
-    }
+                y[(c * 3 + a) * F + t] = msd_unwrap(x[a], n0, n1, n2, cell.cm, a) - first[a][c & 31];
+        });
 }
 
 // Y[a][t] (+)= y of the nb atoms of the batch, one after the other; the first atom of the selection starts the sum
@@ -269,20 +249,6 @@ extern "C" int sit_msd(sit_ctx *c, const double *positions, i64 F, const i64 *at
     if (max_residual) *max_residual = 0.0;
     if (n_sel == 0) return SIT_OK;
     SIT_REQUIRE(c, msd, "sit_msd: missing array");
-    i64 A = n_sel;
-    if (!positions) {
-        SIT_REQUIRE(c, c->d_frames && c->A > 0, "sit_msd: no resident frames (sit_set_frames first)");
-        SIT_REQUIRE(c, F == c->F, "sit_msd: F is not the number of resident frames");
-        SIT_REQUIRE(c, atoms, "sit_msd: the resident frames need an atom list");
-        A = c->A;
-        for (i64 i = 0; i < n_sel; i++)
-            if (atoms[i] < 0 || atoms[i] >= A) {
-                char text[128];
-                snprintf(text, sizeof(text), "sit_msd: atom %lld is outside the %lld atoms of a frame", (long long)atoms[i], (long long)A);
-                c->msg = text;
-                return SIT_ERR_INVALID;
-            }
-    }
     MsdCell cell;
     for (int i = 0; i < 9; i++) { cell.cm[i] = c->pbc.cm[i]; cell.ci[i] = c->pbc.ci[i]; }
     if (unwrap) {
@@ -301,56 +267,37 @@ extern "C" int sit_msd(sit_ctx *c, const double *positions, i64 F, const i64 *at
     const double2 *root = nullptr;
     if (!direct && (rc = sp_roots(c, pl.sp.M, &root))) return rc;
     const i64 B = pl.atoms_per_batch;
-    // one buffer: a status word, the atom list, the lag list, then the plan's workspace
-    const i64 head = 256 + msd_round256(n_sel * 8) + msd_round256(direct ? n_lags * 8 : 0);
     Scoped work(c), upload(c);
-    HIP_TRY(c, sit_dmalloc(c, &work.p, (size_t)(head + pl.workspace)));
-    char *w = (char *)work.p;
-    u64 *d_res = (u64 *)w; w += 256;
-    i64 *d_atoms = (i64 *)w; w += msd_round256(n_sel * 8);
-    i64 *d_lags = (i64 *)w; w += msd_round256(direct ? n_lags * 8 : 0);
-    double *d_coll_y = (double *)w; w += pl.fixed_bytes;
-    double *d_y = (double *)w; w += 3 * B * pl.series_bytes;
-    i32 *d_img = (i32 *)w; w += 3 * B * pl.image_bytes;
-    double *d_psum = (double *)w; w += 3 * B * pl.psum_bytes;
-    void *d_totals = (void *)w; w += 3 * B * pl.chunk_bytes;
-    double2 *d_buf = (double2 *)w; w += direct ? 0 : 3 * B * pl.sp.M * 16;
-    double *d_out = (double *)w; w += 3 * B * msd_round256(n_lags * 8);
-    double *d_r4 = (double *)w;
-    HIP_TRY(c, hipMemsetAsync(d_res, 0, 256, c->stream));
-    const double *d_pos = c->d_frames;
-    if (positions) {
-        HIP_TRY(c, sit_dmalloc(c, &upload.p, (size_t)(F * n_sel) * 24));
-        HIP_TRY(c, hipMemcpyAsync(upload.p, positions, (size_t)(F * n_sel) * 24, hipMemcpyHostToDevice, c->stream));
-        d_pos = (const double *)upload.p;
-    } else {
-        HIP_TRY(c, hipMemcpyAsync(d_atoms, atoms, (size_t)n_sel * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    if (direct) HIP_TRY(c, hipMemcpyAsync(d_lags, lags, (size_t)n_lags * 8, hipMemcpyHostToDevice, c->stream));
+    MsdPieces w;
+    if ((rc = carve_scratch(c, [&](Carve &cv) { w = msd_layout(cv, pl, in, B); }, &work))) return rc;
+    HIP_TRY(c, hipMemsetAsync(w.status, 0, 8, c->stream));
+    SeriesSource src;
+    if ((rc = series_source(c, "sit_msd", positions, F, atoms, n_sel, w.atoms, upload, &src))) return rc;
+    if (direct) HIP_TRY(c, hipMemcpyAsync(w.lags, lags, (size_t)n_lags * 8, hipMemcpyHostToDevice, c->stream));
     std::vector<i32> img_host(images ? (size_t)(3 * B * F) : 0);
     for (i64 a0 = 0; a0 < n_sel; a0 += B) {
         const i64 nb = a0 + B < n_sel ? B : n_sel - a0, n_series = 3 * nb;
         const dim3 tiles((unsigned)((F + 31) / 32), (unsigned)((nb + 31) / 32));
         if (unwrap) {
-            k_msd_shift<<<tiles, dim3(256), 0, c->stream>>>(d_pos, A, positions ? nullptr : d_atoms, a0, nb, F, cell, d_img, d_res);
+            k_msd_shift<<<tiles, dim3(256), 0, c->stream>>>(src, a0, nb, F, cell, w.images, w.status);
             HIP_TRY(c, hipGetLastError());
-            ScanImages si; si.v = d_img; si.F = F;
-            if ((rc = msd_scan(c, si, pl.n_chunks, n_series, (i32 *)d_totals))) return rc;
+            ScanImages si; si.v = w.images; si.F = F;
+            if ((rc = msd_scan(c, si, pl.n_chunks, n_series, (i32 *)w.totals))) return rc;
         }
-        k_msd_series<<<tiles, dim3(256), 0, c->stream>>>(d_pos, A, positions ? nullptr : d_atoms, a0, nb, F, cell, unwrap ? d_img : nullptr, d_y);
+        k_msd_series<<<tiles, dim3(256), 0, c->stream>>>(src, a0, nb, F, cell, unwrap ? w.images : nullptr, w.y);
         HIP_TRY(c, hipGetLastError());
         if (collective) {
-            k_msd_collective<<<dim3((unsigned)((F + 255) / 256), 3), dim3(256), 0, c->stream>>>(d_y, nb, F, a0 == 0 ? 1 : 0, d_coll_y);
+            k_msd_collective<<<dim3((unsigned)((F + 255) / 256), 3), dim3(256), 0, c->stream>>>(w.y, nb, F, a0 == 0 ? 1 : 0, w.coll_y);
             HIP_TRY(c, hipGetLastError());
         }
         if (direct) {
-            k_msd_direct<<<dim3((unsigned)n_lags, (unsigned)nb), dim3(256), 0, c->stream>>>(d_y, F, d_lags, n_lags, d_out, r4 ? d_r4 : nullptr);
+            k_msd_direct<<<dim3((unsigned)n_lags, (unsigned)nb), dim3(256), 0, c->stream>>>(w.y, F, w.lags, n_lags, w.out, r4 ? w.r4 : nullptr);
             HIP_TRY(c, hipGetLastError());
-            if (r4) HIP_TRY(c, hipMemcpyAsync(r4 + a0 * n_lags, d_r4, (size_t)(nb * n_lags) * 8, hipMemcpyDeviceToHost, c->stream));
-        } else if ((rc = msd_all_lags(c, pl, root, d_y, d_psum, (double *)d_totals, d_buf, d_out, F, n_lags, n_series))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(msd + a0 * 3 * n_lags, d_out, (size_t)(n_series * n_lags) * 8, hipMemcpyDeviceToHost, c->stream));
+            if (r4) HIP_TRY(c, hipMemcpyAsync(r4 + a0 * n_lags, w.r4, (size_t)(nb * n_lags) * 8, hipMemcpyDeviceToHost, c->stream));
+        } else if ((rc = msd_all_lags(c, pl, root, w.y, w.psum, (double *)w.totals, (double2 *)w.buf, w.out, F, n_lags, n_series))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(msd + a0 * 3 * n_lags, w.out, (size_t)(n_series * n_lags) * 8, hipMemcpyDeviceToHost, c->stream));
         if (images) {
-            if (unwrap) HIP_TRY(c, hipMemcpyAsync(img_host.data(), d_img, (size_t)(n_series * F) * 4, hipMemcpyDeviceToHost, c->stream));
+            if (unwrap) HIP_TRY(c, hipMemcpyAsync(img_host.data(), w.images, (size_t)(n_series * F) * 4, hipMemcpyDeviceToHost, c->stream));
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             for (i64 i = 0; i < nb; i++)
                 for (i64 t = 0; t < F; t++)
@@ -362,15 +309,15 @@ extern "C" int sit_msd(sit_ctx *c, const double *positions, i64 F, const i64 *at
     if (collective) {
         // the three series of Y through the same kernels, in the first atom's place of the workspace
         if (direct) {
-            k_msd_direct<<<dim3((unsigned)n_lags, 1), dim3(256), 0, c->stream>>>(d_coll_y, F, d_lags, n_lags, d_out, nullptr);
+            k_msd_direct<<<dim3((unsigned)n_lags, 1), dim3(256), 0, c->stream>>>(w.coll_y, F, w.lags, n_lags, w.out, nullptr);
             HIP_TRY(c, hipGetLastError());
-        } else if ((rc = msd_all_lags(c, pl, root, d_coll_y, d_psum, (double *)d_totals, d_buf, d_out, F, n_lags, 3))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(coll, d_out, (size_t)(3 * n_lags) * 8, hipMemcpyDeviceToHost, c->stream));
+        } else if ((rc = msd_all_lags(c, pl, root, w.coll_y, w.psum, (double *)w.totals, (double2 *)w.buf, w.out, F, n_lags, 3))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(coll, w.out, (size_t)(3 * n_lags) * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (i64 i = 0; i < 3 * n_lags; i++) coll[i] /= (double)n_sel;
     }
     u64 bits = 0;
-    HIP_TRY(c, hipMemcpyAsync(&bits, d_res, 8, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&bits, w.status, 8, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (max_residual) { double v; memcpy(&v, &bits, 8); *max_residual = v; }
     return SIT_OK;

@@ -1,6 +1,7 @@
 // Every decision of the mean squared displacement (msd.hip), in ONE place: the rounding of a step to its periodic
 // image, the operation order of the unwrapped position, the chunks of the two scans along the frames and the order of
-// their sums, the windowed term S1, the combination with the autocorrelation, and the atoms per batch.  Host and device
+// their sums, the windowed term S1, the combination with the autocorrelation, the atoms per batch, and - msd_layout(), the
+// one place that names them - the pieces of a call's device buffer, from which the plan takes its byte counts.  Host and device
 // arithmetic only: no HIP call, no context, no side effect (tests/test_msd_plan.py compiles it with g++ under ASan / UBSan).
 //
 // Definitions.  For a selected atom with positions x[t], t = 0..F-1, under the cell with rows c_0..c_2:
@@ -96,10 +97,6 @@ struct MsdPlanIn {
 struct MsdPlan {
     SpPlan sp;                                    // the passes of the transform (n = F, so M >= 2 F - 1); unused when direct
     int64_t n_chunks;
-    int64_t series_bytes;                         // y of one series
-    int64_t image_bytes;                          // N of one series
-    int64_t psum_bytes;                           // P of one series (F + 1 values)
-    int64_t chunk_bytes;                          // chunk totals of one series
     int64_t atom_bytes;                           // workspace of one atom (three series)
     int64_t fixed_bytes;                          // the collective series, whatever the batch
     int64_t atoms_per_batch, n_batches, workspace;
@@ -108,28 +105,53 @@ struct MsdPlan {
 
 inline int64_t msd_round256(int64_t v) { return (v + 255) / 256 * 256; }
 
+// The device buffer of a call: a head, then, from `head` bytes on, the plan's workspace - the collective series, whatever
+// the batch, and for each of the 3 B series of a batch of B atoms y, N, P (F + 1 values), the chunk totals of a scan (int32
+// or float64), the transform's M complex points as (re, im) pairs, the results (msd; r4 is a fourth row of an atom).  A
+// series' piece is sized in whole units of 256 bytes; what is not needed takes nothing.
+struct MsdPieces {
+    unsigned long long *status; int64_t *atoms, *lags;
+    int64_t head;
+    double *coll_y, *y; int32_t *images; double *psum; void *totals; double *buf, *out, *r4;
+};
+
+inline MsdPieces msd_layout(Carve &cv, const MsdPlan &p, const MsdPlanIn &in, int64_t B)
+{
+    const int64_t S = 3 * B, y = msd_round256(in.F * 8) / 8, out = msd_round256(in.n_lags * 8) / 8;
+    MsdPieces w;
+    w.status = cv.take<unsigned long long>(1, 256);
+    w.atoms = cv.take<int64_t>(in.n_sel, 256);
+    w.lags = cv.take<int64_t>(in.direct ? in.n_lags : 0, 256);
+    cv.take<char>(0, 256);
+    w.head = cv.used;
+    w.coll_y = cv.take<double>(in.collective ? 3 * y : 0);
+    w.y = cv.take<double>(S * y);
+    w.images = cv.take<int32_t>(S * (msd_round256(in.F * 4) / 4));
+    w.psum = cv.take<double>(in.direct ? 0 : S * (msd_round256((in.F + 1) * 8) / 8));
+    w.totals = cv.take<double>(S * (msd_round256(p.n_chunks * 8) / 8));
+    w.buf = cv.take<double>(in.direct ? 0 : S * p.sp.M * 2);
+    w.out = cv.take<double>(S * out);
+    w.r4 = cv.take<double>(in.direct ? B * out : 0);
+    return w;
+}
+
 inline MsdPlan msd_plan(const MsdPlanIn &in, const SpKnobs &k)
 {
     MsdPlan p = MsdPlan();
     if (in.F < 2 || in.F > MSD_MAX_F) { p.err = "the mean squared displacement needs 2 to 2^29 frames"; return p; }
     if (in.n_lags < 1 || in.n_sel < 0) { p.err = "no lag"; return p; }
     p.n_chunks = msd_chunks(in.F);
-    p.series_bytes = msd_round256(in.F * 8);
-    p.image_bytes = msd_round256(in.F * 4);
-    p.psum_bytes = in.direct ? 0 : msd_round256((in.F + 1) * 8);
-    p.chunk_bytes = msd_round256(p.n_chunks * 8);
-    int64_t transform = 0;
     if (!in.direct) {
         SpPlanIn si;
         si.n = in.F; si.n_sel = 1; si.workspace_bytes = (int64_t)1 << 62; si.want_spectrum = false;
         p.sp = sp_plan(si, k);
         if (p.sp.err) { p.err = p.sp.err; return p; }
-        transform = p.sp.M * 16;
     }
-    // per series: y, N, P, the chunk totals of a scan, the transform's points, the results (msd; r4 is a fourth row)
-    const int64_t out = msd_round256(in.n_lags * 8);
-    p.atom_bytes = 3 * (p.series_bytes + p.image_bytes + p.psum_bytes + p.chunk_bytes + transform + out) + (in.direct ? out : 0);
-    p.fixed_bytes = in.collective ? 3 * p.series_bytes : 0;
+    Carve none = {nullptr, 0}, one = {nullptr, 0};
+    const int64_t head = msd_layout(none, p, in, 0).head;
+    msd_layout(one, p, in, 1);
+    p.fixed_bytes = none.used - head;
+    p.atom_bytes = one.used - none.used;
     const int64_t cap = in.workspace_bytes > 0 ? in.workspace_bytes : k.workspace;
     int64_t b = (cap - p.fixed_bytes) / p.atom_bytes;
     if (cap < p.fixed_bytes || b < 1) { p.err = "the workspace cap is below one atom's series and transform"; return p; }

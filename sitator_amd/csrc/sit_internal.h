@@ -160,7 +160,7 @@ struct sit_ctx {
     void *d_scratch = nullptr;
     i64 scratch_bytes = 0;
     void *fill_ring = nullptr;        // results of deferred fills not yet collected (fill.hip)
-    void *spectrum = nullptr;         // tables and buffers of sit_speed_spectrum (spectrum.hip); opaque here
+    void *spectrum = nullptr;         // tables of the pass kernel of spectrum.hip (sit_speed_spectrum, sit_msd); opaque here
     void *group = nullptr;            // the grouping of sit_group_by_site (group.hip); opaque here
     void *voronoi = nullptr;          // the result of the last sit_voronoi_nodes (voronoi.hip); opaque here
     void *coordenv = nullptr;         // the result of the last sit_coordination_environments (coordenv.hip); opaque here
@@ -238,19 +238,6 @@ static inline int ensure_scratch(sit_ctx *c, i64 bytes)
     return SIT_OK;
 }
 
-// The layout `lay(Carve &)` of an entry point's scratch: run once to size the buffer, once more to hand out its pieces
-template <class Lay>
-static int carve_scratch(sit_ctx *c, Lay lay)
-{
-    Carve cv = {nullptr, 0};
-    lay(cv);
-    const int rc = ensure_scratch(c, cv.used);
-    if (rc) return rc;
-    cv = {(char *)c->d_scratch, 0};
-    lay(cv);
-    return SIT_OK;
-}
-
 // a pool buffer of one call, back to the pool on every way out
 struct Scoped {
     sit_ctx *c;
@@ -259,6 +246,20 @@ struct Scoped {
     Scoped(const Scoped &) = delete;
     ~Scoped() { if (p) sit_dfree(c, p); }
 };
+
+// The layout `lay(Carve &)` of an entry point's scratch: run once to size the buffer, once more to hand out its pieces.
+// The buffer is the context's scratch, or - `buf` - a pool buffer of the call
+template <class Lay>
+static int carve_scratch(sit_ctx *c, Lay lay, Scoped *buf = nullptr)
+{
+    Carve cv = {nullptr, 0};
+    lay(cv);
+    if (buf) HIP_TRY(c, sit_dmalloc(c, &buf->p, (size_t)cv.used));
+    else if (const int rc = ensure_scratch(c, cv.used)) return rc;
+    cv = {(char *)(buf ? buf->p : c->d_scratch), 0};
+    lay(cv);
+    return SIT_OK;
+}
 
 // numpy's IndexError text for a site index beyond a table of K sites (_lib.py matches on its first word)
 static inline int index_out_of_bounds(sit_ctx *c, i64 index, i64 K)
@@ -526,32 +527,6 @@ __host__ __device__ inline double exact_value(u64 hi, u64 lo)
     const double v = h + ldexp((double)lo, -80);
     return neg ? -v : v;
 }
-
-// ---- the pass kernel of spectrum.hip, shared with msd.hip: what a launch fuses, and its arguments ----
-enum { SP_LOAD_PLAIN = 0, SP_LOAD_FIRST = 1, SP_LOAD_UNTWIDDLE = 2, SP_LOAD_REAL = 3 };
-enum { SP_MID_FWD = 1, SP_MID_INV = 2, SP_MID_CONV = 3, SP_MID_POWER = 7 };          // bit 0: forward, bit 1: inverse
-enum { SP_STORE_PLAIN = 0, SP_STORE_TWIDDLE = 1, SP_STORE_BAND = 2, SP_STORE_MSD = 3 };
-
-struct SpArgs {
-    double2 *buf;                  // [atoms of the batch][M], transformed in place
-    const double *speeds;          // [atoms of the batch][n]   (SP_LOAD_REAL: any real series of length n)
-    const double2 *chirp;          // [n]   w_j
-    const double2 *root;           // [M]   exp(-2 pi i e / M)
-    const double2 *filter;         // [M]   B, in the order the forward passes leave
-    const double *freqs;           // [nbins]
-    const unsigned char *fmask;    // [nbins]
-    double *partial;               // [atoms of the batch][tiles][2]
-    double2 *spec;                 // [atoms of the batch][nbins] or null
-    const double *psum;            // SP_STORE_MSD: [series][n + 1] prefix sums of the squares
-    double *msd;                   // SP_STORE_MSD: [series][nbins], nbins = lags kept
-    i64 n, M, nbins, L, S, tiles;
-    int bits, log_s, lines, log_lines, pad, load, mid, store;
-    double inv_m;
-};
-struct SpPlan;                     // spectrum_plan.h
-// one pass of level `level` of the plan over nb lines of M points (grid.y); the M-th roots alone (kept with the context)
-int sp_launch(sit_ctx *c, const SpPlan &pl, int level, SpArgs a, int load, int mid, int store, i64 nb);
-int sp_roots(sit_ctx *c, i64 M, const double2 **root);
 
 // host-side pieces implemented in other translation units
 int sit_predict_internal(sit_ctx *c, double threshold, bool words_reset = false);   // words_reset: predict_reset_with_fill did it

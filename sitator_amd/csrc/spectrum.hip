@@ -20,35 +20,27 @@
 // M <= 2^10: one launch per batch of atoms; M <= 2^20: three; M <= 2^30: five.  Every atom's transform is its own - an
 // atom's arithmetic does not depend on which atoms share a launch - and the band sums are reduced in a fixed order:
 // per thread in index order, a tree over the workgroup, the workgroups of an atom one after the other.
+//
+// Where the selected atoms come from and the tile that makes their speeds are in series.h (shared with msd.hip), the pieces
+// of a call's buffer in sp_layout (spectrum_plan.h), what msd.hip needs of the pass kernel in spectrum_pass.h.
 #include <cmath>
-#include <cstdio>
 
-#include "sit_internal.h"
-#include "spectrum_plan.h"
+#include "series.h"
+#include "spectrum_pass.h"
 #include "msd_plan.h"
 
 // speeds[c][t] = |x[t+1][atom_c] - x[t][atom_c]| for the atoms [a0, a0 + nb) of the selection, in the reference's
-// operation order (a plain difference, sqrt((dx^2 + dy^2) + dz^2)).  A 32 x 32 tile: read with the atoms across lanes
-// (neighbours in a frame), written with the frames across lanes (the transform reads an atom's speeds as one run).
-__global__ __launch_bounds__(256) void k_spec_speeds(const double *pos, i64 A, const i64 *atoms, i64 a0, i64 nb, i64 n, double *speeds)
+// operation order (a plain difference, sqrt((dx^2 + dy^2) + dz^2)), through the tile of series.h (the transform reads an
+// atom's speeds as one run).
+__global__ __launch_bounds__(256) void k_spec_speeds(SeriesSource src, i64 a0, i64 nb, i64 n, double *speeds)
 {
-    __shared__ double tile[32][33];
-    const i64 t0 = (i64)blockIdx.x * 32, c0 = (i64)blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-    for (int r = ty; r < 32; r += 8) {
-        const i64 t = t0 + r, c = c0 + tx;
-        if (t < n && c < nb) {
-            const i64 atom = atoms ? atoms[a0 + c] : a0 + c;
-            const double *p0 = pos + (t * A + atom) * 3, *p1 = p0 + A * 3;
+    series_tile<1, double>(a0, nb, n,
+        [&](i64 t, i64 column, double *v) {
+            const double *p0 = src.at(t, column), *p1 = p0 + src.A * 3;
             const double dx = p1[0] - p0[0], dy = p1[1] - p0[1], dz = p1[2] - p0[2];
-            tile[r][tx] = sqrt((dx * dx + dy * dy) + dz * dz);
-        }
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const i64 c = c0 + r, t = t0 + tx;
-        if (t < n && c < nb) speeds[c * n + t] = tile[tx][r];
-    }
+            v[0] = sqrt((dx * dx + dy * dy) + dz * dz);
+        },
+        [&](i64 t, i64 c, const double *v) { speeds[c * n + t] = v[0]; });
 }
 
 __device__ __forceinline__ i64 sp_bitrev(i64 l, int bits) { return bits ? (i64)(__brev((unsigned)l) >> (32 - bits)) : 0; }
@@ -205,34 +197,20 @@ __global__ void k_spec_finish(const double *partial, i64 tiles, i64 nb, double *
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
 
-// What a context keeps between calls: the tables of the last transform length (chirp, M-th roots of unity, transformed
-// filter) and its buffers.  Nothing here is read by any other entry point.
+// What a context keeps between calls: the chirp and the transformed filter of the last transform length, and the one
+// table of M-th roots of unity that every pass reads (sp_roots).  The buffers of a call are pool buffers of that call.
 struct SpState {
-    i64 n = 0;                                  // the length the tables were made for (0: none)
-    double2 *chirp = nullptr, *root = nullptr, *filter = nullptr;
-    i64 chirp_cap = 0, root_cap = 0, filter_cap = 0;
-    i64 roots_m = 0;                            // sp_roots: the M its table was made for (0: none)
+    i64 n = 0;                                  // the length chirp and filter were made for (0: none)
+    double2 *chirp = nullptr, *filter = nullptr;
+    i64 roots_m = 0;                            // the M the roots were made for (0: none)
     double2 *roots = nullptr;
-    i64 roots_cap = 0;
-    void *work = nullptr, *aux = nullptr, *pos = nullptr;
-    i64 work_cap = 0, aux_cap = 0, pos_cap = 0;
 };
-
-static int sp_grow(sit_ctx *c, void **p, i64 *cap, i64 bytes)
-{
-    if (bytes <= *cap) return SIT_OK;
-    if (*p) { sit_dfree(c, *p); *p = nullptr; *cap = 0; }
-    HIP_TRY(c, sit_dmalloc(c, p, (size_t)bytes));
-    *cap = bytes;
-    return SIT_OK;
-}
 
 void spectrum_free(sit_ctx *c)
 {
     SpState *st = (SpState *)c->spectrum;
     if (!st) return;
-    void *ptrs[] = {st->chirp, st->root, st->filter, st->roots, st->work, st->aux, st->pos};
-    for (void *p : ptrs) if (p) sit_dfree(c, p);
+    for (void *p : {(void *)st->chirp, (void *)st->filter, (void *)st->roots}) if (p) sit_dfree(c, p);
     delete st;
     c->spectrum = nullptr;
 }
@@ -250,19 +228,9 @@ int sp_launch(sit_ctx *c, const SpPlan &pl, int level, SpArgs a, int load, int m
     return SIT_OK;
 }
 
-// tab[e] = exp(-2 pi i e / M), M = tab.size(), in extended precision and rounded once
-static void sp_root_values(std::vector<double2> &tab)
-{
-    const long double pi = 3.141592653589793238462643383279502884L;
-    const i64 M = (i64)tab.size();
-    for (i64 e = 0; e < M; e++) {
-        const long double ph = 2.0L * pi * ((long double)e / (long double)M);
-        tab[(size_t)e] = make_double2((double)cosl(ph), (double)-sinl(ph));
-    }
-}
-
-// The M-th roots of unity alone, for a transform that needs neither chirp nor filter (msd.hip): made as sp_tables makes
-// them, kept with the context until another M is asked for.
+// The M-th roots of unity that every pass reads, the spectrum's and the autocorrelation's of msd.hip: one table,
+// tab[e] = exp(-2 pi i e / M) in extended precision and rounded once, kept with the context until another M is asked for -
+// so whoever launches a pass asks for it first, on every call.
 int sp_roots(sit_ctx *c, i64 M, const double2 **root)
 {
     if (!c->spectrum) c->spectrum = new SpState();
@@ -270,9 +238,13 @@ int sp_roots(sit_ctx *c, i64 M, const double2 **root)
     if (st->roots_m != M) {
         st->roots_m = 0;
         int rc;
-        if ((rc = sp_grow(c, (void **)&st->roots, &st->roots_cap, M * 16))) return rc;
+        if ((rc = dev_alloc(c, &st->roots, M))) return rc;
+        const long double pi = 3.141592653589793238462643383279502884L;
         std::vector<double2> tab((size_t)M);
-        sp_root_values(tab);
+        for (i64 e = 0; e < M; e++) {
+            const long double ph = 2.0L * pi * ((long double)e / (long double)M);
+            tab[(size_t)e] = make_double2((double)cosl(ph), (double)-sinl(ph));
+        }
         HIP_TRY(c, hipMemcpyAsync(st->roots, tab.data(), (size_t)M * 16, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         st->roots_m = M;
@@ -282,29 +254,23 @@ int sp_roots(sit_ctx *c, i64 M, const double2 **root)
 }
 
 // The tables of length n, made on the host in extended precision and rounded once: the chirp with its phase reduced in
-// integers (j^2 mod 2n; j^2 pi / n in floating point is already 1e-11 off at j = 1e5), the M-th roots of unity, and the
-// filter conj(w_j) wrapped round M, which the forward passes then transform where it lies.
-static int sp_tables(sit_ctx *c, SpState *st, const SpPlan &pl, i64 n)
+// integers (j^2 mod 2n; j^2 pi / n in floating point is already 1e-11 off at j = 1e5) and the filter conj(w_j) wrapped
+// round M, which the forward passes then transform where it lies, with the roots of sp_roots.
+static int sp_tables(sit_ctx *c, SpState *st, const SpPlan &pl, i64 n, const double2 *root)
 {
     if (st->n == n) return SIT_OK;
     st->n = 0;
     const i64 M = pl.M;
     int rc;
-    if ((rc = sp_grow(c, (void **)&st->chirp, &st->chirp_cap, n * 16))) return rc;
-    if ((rc = sp_grow(c, (void **)&st->root, &st->root_cap, M * 16))) return rc;
-    if ((rc = sp_grow(c, (void **)&st->filter, &st->filter_cap, M * 16))) return rc;
+    if ((rc = dev_alloc(c, &st->chirp, n)) || (rc = dev_alloc(c, &st->filter, M))) return rc;
     const long double pi = 3.141592653589793238462643383279502884L;
-    std::vector<double2> chirp((size_t)n), tab((size_t)M);
+    std::vector<double2> chirp((size_t)n), tab((size_t)M, make_double2(0.0, 0.0));
     for (i64 j = 0; j < n; j++) {
         const u64 r = ((u64)j * (u64)j) % (u64)(2 * n);
         const long double ph = pi * (long double)r / (long double)n;
         chirp[(size_t)j] = make_double2((double)cosl(ph), (double)-sinl(ph));
     }
     HIP_TRY(c, hipMemcpyAsync(st->chirp, chirp.data(), (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
-    sp_root_values(tab);
-    HIP_TRY(c, hipMemcpyAsync(st->root, tab.data(), (size_t)M * 16, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));                             // tab is reused
-    for (i64 e = 0; e < M; e++) tab[(size_t)e] = make_double2(0.0, 0.0);
     for (i64 j = 0; j < n; j++) {
         const double2 b = make_double2(chirp[(size_t)j].x, -chirp[(size_t)j].y);
         tab[(size_t)j] = b;
@@ -312,7 +278,7 @@ static int sp_tables(sit_ctx *c, SpState *st, const SpPlan &pl, i64 n)
     }
     HIP_TRY(c, hipMemcpyAsync(st->filter, tab.data(), (size_t)M * 16, hipMemcpyHostToDevice, c->stream));
     SpArgs a = SpArgs();
-    a.buf = st->filter; a.root = st->root; a.n = n; a.M = M; a.nbins = pl.nbins;
+    a.buf = st->filter; a.root = root; a.n = n; a.M = M; a.nbins = pl.nbins;
     for (int i = 0; i < pl.npass; i++)
         if ((rc = sp_launch(c, pl, i, a, SP_LOAD_PLAIN, SP_MID_FWD, SP_STORE_TWIDDLE, 1))) return rc;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -331,62 +297,32 @@ extern "C" int sit_speed_spectrum(sit_ctx *c, const double *positions, i64 F, co
     if (n_sel == 0) return SIT_OK;
     SIT_REQUIRE(c, freqs && fmask && avg && band_power, "sit_speed_spectrum: missing array");
     const i64 n = F - 1;
-    i64 A = n_sel;
-    if (!positions) {
-        SIT_REQUIRE(c, c->d_frames && c->A > 0, "sit_speed_spectrum: no resident frames (sit_set_frames first)");
-        SIT_REQUIRE(c, F == c->F, "sit_speed_spectrum: F is not the number of resident frames");
-        SIT_REQUIRE(c, atoms, "sit_speed_spectrum: the resident frames need an atom list");
-        A = c->A;
-        for (i64 i = 0; i < n_sel; i++)
-            if (atoms[i] < 0 || atoms[i] >= A) {
-                char text[128];
-                snprintf(text, sizeof(text), "sit_speed_spectrum: atom %lld is outside the %lld atoms of a frame", (long long)atoms[i], (long long)A);
-                c->msg = text;
-                return SIT_ERR_INVALID;
-            }
-    }
     SpPlanIn in;
     in.n = n; in.n_sel = n_sel; in.workspace_bytes = workspace_bytes; in.want_spectrum = spectrum != nullptr;
     const SpPlan pl = sp_plan(in, sp_knobs_from_env());
     if (pl.err) { c->msg = std::string("sit_speed_spectrum: ") + pl.err; return SIT_ERR_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->spectrum) c->spectrum = new SpState();
-    SpState *st = (SpState *)c->spectrum;
     int rc;
-    if ((rc = sp_tables(c, st, pl, n))) return rc;
+    const double2 *root = nullptr;
+    if ((rc = sp_roots(c, pl.M, &root))) return rc;
+    SpState *st = (SpState *)c->spectrum;                                    // sp_roots made it
+    if ((rc = sp_tables(c, st, pl, n, root))) return rc;
     const i64 nbins = pl.nbins, B = pl.atoms_per_batch, tiles = pl.pass[0].tiles;
-    if ((rc = sp_grow(c, &st->work, &st->work_cap, pl.workspace))) return rc;
-    const i64 fm_bytes = (nbins + 7) / 8 * 8;
-    if ((rc = sp_grow(c, &st->aux, &st->aux_cap, nbins * 8 + fm_bytes + n_sel * 8))) return rc;
-    double *d_freqs = (double *)st->aux;
-    unsigned char *d_fmask = (unsigned char *)st->aux + nbins * 8;
-    i64 *d_atoms = (i64 *)((char *)st->aux + nbins * 8 + fm_bytes);
-    HIP_TRY(c, hipMemcpyAsync(d_freqs, freqs, (size_t)nbins * 8, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(d_fmask, fmask, (size_t)nbins, hipMemcpyHostToDevice, c->stream));
-    const double *d_pos = c->d_frames;
-    if (positions) {
-        if ((rc = sp_grow(c, &st->pos, &st->pos_cap, F * n_sel * 24))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(st->pos, positions, (size_t)(F * n_sel) * 24, hipMemcpyHostToDevice, c->stream));
-        d_pos = (const double *)st->pos;
-    } else {
-        HIP_TRY(c, hipMemcpyAsync(d_atoms, atoms, (size_t)n_sel * 8, hipMemcpyHostToDevice, c->stream));
-    }
-    // the workspace of a batch, every part a multiple of 16 bytes but the last
-    char *w = (char *)st->work;
-    double2 *d_buf = (double2 *)w; w += B * pl.M * 16;
-    double2 *d_spec = spectrum ? (double2 *)w : nullptr; w += spectrum ? B * nbins * 16 : 0;
-    double *d_partial = (double *)w; w += B * tiles * 16;
-    double *d_result = (double *)w; w += B * 16;
-    double *d_speeds = (double *)w;
+    Scoped work(c), upload(c);
+    SpPieces w;
+    if ((rc = carve_scratch(c, [&](Carve &cv) { w = sp_layout(cv, pl, in, B); }, &work))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(w.freqs, freqs, (size_t)nbins * 8, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(w.fmask, fmask, (size_t)nbins, hipMemcpyHostToDevice, c->stream));
+    SeriesSource src;
+    if ((rc = series_source(c, "sit_speed_spectrum", positions, F, atoms, n_sel, w.atoms, upload, &src))) return rc;
     std::vector<double> result((size_t)(2 * B));
     SpArgs a = SpArgs();
-    a.buf = d_buf; a.speeds = d_speeds; a.chirp = st->chirp; a.root = st->root; a.filter = st->filter; a.freqs = d_freqs;
-    a.fmask = d_fmask; a.partial = d_partial; a.spec = d_spec; a.n = n; a.M = pl.M; a.nbins = nbins; a.inv_m = 1.0 / (double)pl.M;
+    a.buf = (double2 *)w.buf; a.speeds = w.speeds; a.chirp = st->chirp; a.root = root; a.filter = st->filter; a.freqs = w.freqs;
+    a.fmask = w.fmask; a.partial = w.partial; a.spec = (double2 *)w.spec; a.n = n; a.M = pl.M; a.nbins = nbins; a.inv_m = 1.0 / (double)pl.M;
     const int p = pl.npass;
     for (i64 a0 = 0; a0 < n_sel; a0 += B) {
         const i64 nb = a0 + B < n_sel ? B : n_sel - a0;
-        k_spec_speeds<<<dim3((unsigned)((n + 31) / 32), (unsigned)((nb + 31) / 32)), dim3(256), 0, c->stream>>>(
-            d_pos, A, positions ? nullptr : d_atoms, a0, nb, n, d_speeds);
+        k_spec_speeds<<<dim3((unsigned)((n + 31) / 32), (unsigned)((nb + 31) / 32)), dim3(256), 0, c->stream>>>(src, a0, nb, n, w.speeds);
         HIP_TRY(c, hipGetLastError());
         for (int i = 0; i < p - 1; i++)
             if ((rc = sp_launch(c, pl, i, a, i == 0 ? SP_LOAD_FIRST : SP_LOAD_PLAIN, SP_MID_FWD, SP_STORE_TWIDDLE, nb))) return rc;
@@ -394,11 +330,11 @@ extern "C" int sit_speed_spectrum(sit_ctx *c, const double *positions, i64 F, co
             return rc;
         for (int i = p - 2; i >= 0; i--)
             if ((rc = sp_launch(c, pl, i, a, SP_LOAD_UNTWIDDLE, SP_MID_INV, i == 0 ? SP_STORE_BAND : SP_STORE_PLAIN, nb))) return rc;
-        k_spec_finish<<<dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, c->stream>>>(d_partial, tiles, nb, d_result);
+        k_spec_finish<<<dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, c->stream>>>(w.partial, tiles, nb, w.result);
         HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(result.data(), d_result, (size_t)nb * 16, hipMemcpyDeviceToHost, c->stream));
-        if (spectrum) HIP_TRY(c, hipMemcpyAsync(spectrum + a0 * nbins * 2, d_spec, (size_t)(nb * nbins) * 16, hipMemcpyDeviceToHost, c->stream));
-        if (speeds) HIP_TRY(c, hipMemcpyAsync(speeds + a0 * n, d_speeds, (size_t)(nb * n) * 8, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(result.data(), w.result, (size_t)nb * 16, hipMemcpyDeviceToHost, c->stream));
+        if (spectrum) HIP_TRY(c, hipMemcpyAsync(spectrum + a0 * nbins * 2, w.spec, (size_t)(nb * nbins) * 16, hipMemcpyDeviceToHost, c->stream));
+        if (speeds) HIP_TRY(c, hipMemcpyAsync(speeds + a0 * n, w.speeds, (size_t)(nb * n) * 8, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         for (i64 i = 0; i < nb; i++) { avg[a0 + i] = result[(size_t)(2 * i)]; band_power[a0 + i] = result[(size_t)(2 * i + 1)]; }
     }

@@ -1,6 +1,7 @@
 // The launch plan of the speed power spectrum (spectrum.hip), decided in ONE place: sp_plan() takes the transform length
 // and the SITATOR_SPECTRUM_* knobs and returns the padded length, the passes, the LDS of every pass, the atoms per batch
-// and the workspace.  Host arithmetic only: no HIP call, no context, no side effect (tests/test_vibfreq_ref.py compiles
+// and the workspace; sp_layout() is the one place that names the pieces of a call's device buffer, and the plan takes its
+// byte counts from it.  Host arithmetic only: no HIP call, no context, no side effect (tests/test_vibfreq_ref.py compiles
 // it with g++).
 //
 // Bluestein: a transform of arbitrary length n is a circular convolution of length M = 2^m >= 2n - 1.  The M points of
@@ -11,6 +12,8 @@
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
+
+#include "scratch_carve.h"
 
 #define SP_MAX_PASS 3
 #define SP_MAX_STAGE_BITS 10                      // a 1024-point complex float64 line is 16 KB of LDS
@@ -80,6 +83,31 @@ inline size_t sp_lds_bytes(int64_t L, int lines)
     return (size_t)(2 * lines * (L + sp_pad(lines)) + 2 * half + 2 * SP_THREADS) * 8;
 }
 
+// The device buffer of a call: a head that every batch reads, then, from `head` bytes on, the workspace of a batch of B
+// atoms - per atom the M complex points (transformed in place; complex arrays are (re, im) pairs), the bins when they are
+// asked for, the band sums of every workgroup of the last inverse pass, the result pair and the n speeds.
+struct SpPieces {
+    double *freqs; unsigned char *fmask; int64_t *atoms;
+    int64_t head;
+    double *buf, *spec, *partial, *result, *speeds;
+};
+
+inline SpPieces sp_layout(Carve &cv, const SpPlan &p, const SpPlanIn &in, int64_t B)
+{
+    SpPieces w;
+    w.freqs = cv.take<double>(p.nbins);
+    w.fmask = cv.take<unsigned char>(p.nbins);
+    w.atoms = cv.take<int64_t>(in.n_sel);
+    cv.take<char>(0, 256);
+    w.head = cv.used;
+    w.buf = cv.take<double>(B * p.M * 2);
+    w.spec = in.want_spectrum ? cv.take<double>(B * p.nbins * 2) : nullptr;
+    w.partial = cv.take<double>(B * p.pass[0].tiles * 2);
+    w.result = cv.take<double>(B * 2);
+    w.speeds = cv.take<double>(B * in.n);
+    return w;
+}
+
 inline SpPlan sp_plan(const SpPlanIn &in, const SpKnobs &k)
 {
     SpPlan p = SpPlan();
@@ -107,10 +135,10 @@ inline SpPlan sp_plan(const SpPlanIn &in, const SpKnobs &k)
         q.lds = sp_lds_bytes(q.L, q.lines);
         if (q.lds > SP_LDS_LIMIT) { p.err = "a pass of the spectrum does not fit in LDS"; return p; }
     }
-    // per atom: the M complex points (transformed in place), the n speeds, the band sums of every workgroup of the last
-    // inverse pass, the result pair, and the bins when they are asked for
-    p.atom_bytes = p.M * 16 + in.n * 8 + p.pass[0].tiles * 16 + 16 + (in.want_spectrum ? p.nbins * 16 : 0);
-    p.atom_bytes = (p.atom_bytes + 255) / 256 * 256;
+    // per atom: what a batch of one takes beyond the head, in units of 256 bytes
+    Carve one = {nullptr, 0};
+    const int64_t head = sp_layout(one, p, in, 1).head;
+    p.atom_bytes = (one.used - head + 255) / 256 * 256;
     const int64_t cap = in.workspace_bytes > 0 ? in.workspace_bytes : k.workspace;
     int64_t b = cap / p.atom_bytes;
     if (b < 1) { p.err = "the workspace cap is below one atom's transform"; return p; }

@@ -522,6 +522,30 @@ class ReplaceUnassignedPositions(object):
         return st._derive(new_sn, out, st._confs)
 
 
+def _selected_columns(traj, mask):
+    """The front of a frame-series operator on a host trajectory: ``traj`` as an array, refused unless it is
+    ``[n_frames, n_atoms, 3]`` float64, and ``traj[:, mask]``, contiguous - a copy: the caller's array stays as it is."""
+    traj = np.asarray(traj)
+    if traj.ndim != 3 or traj.shape[2] != 3:
+        raise ValueError("Wrong shape %s for traj." % (traj.shape,))
+    if traj.dtype != np.float64:
+        raise ValueError("Buffer dtype mismatch, expected 'double' but got '%s'" % traj.dtype)
+    selected = np.ascontiguousarray(traj[:, mask])
+    if selected.ndim != 3:
+        raise ValueError("`mask` must select along the atoms")
+    return selected
+
+
+def _resident_columns(la, mask, who):
+    """The front on the frames an analysis left resident: ``(context, atom list)``; ``mask=None``: the mobile atoms."""
+    la._need_run()
+    if getattr(la, "_children", None) is not None or la._comm.size > 1 or la._ctx is None:
+        raise NotImplementedError("%s needs all frames of the trajectory on one GPU; this analysis ran over frame shards" % who)
+    if mask is None:
+        return la._ctx, np.asarray(la._mobile_idx, dtype=np.int64)
+    return la._ctx, np.arange(la._ctx.A, dtype=np.int64)[mask]      # numpy's rules: length, negative indices, bounds
+
+
 class AverageVibrationalFrequency(object):
     """Average vibrational frequency of chosen atoms of a trajectory: the power spectrum of each atom's speed
     ``|x[t+1] - x[t]|`` gives a power-weighted mean frequency over ``min_frequency < f < max_frequency`` (units of
@@ -567,15 +591,8 @@ class AverageVibrationalFrequency(object):
         Raises ``AssertionError("Trajectory too short?")`` when no frequency lies in the band (always with two frames),
         ``ValueError`` for fewer than two frames or another dtype, ``ZeroDivisionError`` when a chosen atom never
         moves (its band holds no power)."""
-        traj = np.asarray(traj)
-        if traj.ndim != 3 or traj.shape[2] != 3:
-            raise ValueError("Wrong shape %s for traj." % (traj.shape,))
-        if traj.dtype != np.float64:
-            raise ValueError("Buffer dtype mismatch, expected 'double' but got '%s'" % traj.dtype)
-        freqs, fmask = self._band(traj.shape[0])
-        selected = np.ascontiguousarray(traj[:, mask])             # a copy: the caller's array stays as it is
-        if selected.ndim != 3:
-            raise ValueError("`mask` must select along the atoms")
+        selected = _selected_columns(traj, mask)
+        freqs, fmask = self._band(len(selected))
         if selected.shape[1] == 0:
             return self._over_atoms(np.empty(0), np.empty(0), return_stdev)
         ctx = _lib.HipContext(np.eye(3))                           # no cell enters: the differences are not wrapped
@@ -594,19 +611,11 @@ class AverageVibrationalFrequency(object):
         shift per frame changes the differences between frames, these are not the caller's frames any more) and
         ``NotImplementedError`` after a run over frame shards (``comm`` of more than one rank, ``devices=[...]`` of more
         than one GPU): a spectrum does not split over the frames."""
-        la._need_run()
-        if getattr(la, "_children", None) is not None or la._comm.size > 1 or la._ctx is None:
-            raise NotImplementedError("AverageVibrationalFrequency needs all frames of the trajectory on one GPU; "
-                                      "this analysis ran over frame shards")
+        ctx, atoms = _resident_columns(la, mask, "AverageVibrationalFrequency")
         if la._recenter_masses is not None:
             raise ValueError("The analysis recentred its frames on the device (recenter_masses): they are not the "
                              "trajectory run() was given; use compute_avg_vibrational_freq on that")
-        ctx = la._ctx
         freqs, fmask = self._band(ctx.F)
-        if mask is None:
-            atoms = np.asarray(la._mobile_idx, dtype=np.int64)
-        else:
-            atoms = np.arange(ctx.A, dtype=np.int64)[mask]         # numpy's rules: length, negative indices, bounds
         if len(atoms) == 0:
             return self._over_atoms(np.empty(0), np.empty(0), return_stdev)
         avg_freqs, band_power, _, _ = ctx.speed_spectrum(freqs, fmask, atoms=atoms)
@@ -846,22 +855,15 @@ class MeanSquaredDisplacement(object):
         vectors (looked at only with ``unwrap``); ``mask``: the atoms, a boolean mask or an index array (whatever
         ``traj[:, mask]`` takes).  Returns an ``MSDResult``.  ``ValueError`` for fewer than two frames, another dtype, a lag
         beyond ``n_frames - 1`` or a degenerate cell."""
-        traj = np.asarray(traj)
-        if traj.ndim != 3 or traj.shape[2] != 3:
-            raise ValueError("Wrong shape %s for traj." % (traj.shape,))
-        if traj.dtype != np.float64:
-            raise ValueError("Buffer dtype mismatch, expected 'double' but got '%s'" % traj.dtype)
-        selected = np.ascontiguousarray(traj[:, mask])             # a copy: the caller's array stays as it is
-        if selected.ndim != 3:
-            raise ValueError("`mask` must select along the atoms")
+        selected = _selected_columns(traj, mask)
         if selected.shape[1] == 0:
-            return self._empty(traj.shape[0], images)
+            return self._empty(len(selected), images)
         ctx = _lib.HipContext(np.asarray(cell, dtype=np.float64) if self.unwrap else np.eye(3))
         try:
             raw = self._call(ctx, images, positions=selected)
         finally:
             ctx.close()
-        return self._result(traj.shape[0], raw)
+        return self._result(len(selected), raw)
 
     def compute_for_analysis(self, la, mask=None, images=False):
         """The same from the trajectory a ``LandmarkAnalysis`` that has run left on its GPU, under that analysis' cell: no
@@ -873,15 +875,7 @@ class MeanSquaredDisplacement(object):
         relative to the framework is what one wants from a cell that drifts.  ``NotImplementedError`` after a run over
         frame shards (``comm`` of more than one rank, ``devices=[...]`` of more than one GPU): a lag reaches across the
         shards."""
-        la._need_run()
-        if getattr(la, "_children", None) is not None or la._comm.size > 1 or la._ctx is None:
-            raise NotImplementedError("MeanSquaredDisplacement needs all frames of the trajectory on one GPU; "
-                                      "this analysis ran over frame shards")
-        ctx = la._ctx
-        if mask is None:
-            atoms = np.asarray(la._mobile_idx, dtype=np.int64)
-        else:
-            atoms = np.arange(ctx.A, dtype=np.int64)[mask]         # numpy's rules: length, negative indices, bounds
+        ctx, atoms = _resident_columns(la, mask, "MeanSquaredDisplacement")
         if len(atoms) == 0:
             return self._empty(ctx.F, images)
         return self._result(ctx.F, self._call(ctx, images, atoms=atoms))

@@ -239,7 +239,7 @@ def test_batches_and_neighbours_do_not_change_an_atom(crowd, direct):
         assert same(whole[:2], ctx.msd(positions=pos, workspace_bytes=ab, **kw)[:2])
 
 
-@pytest.mark.parametrize("n_sel", [1, 3, 65])
+@pytest.mark.parametrize("n_sel", [1, 3, 31, 32, 33, 65])             # 31, 32, 33: the edges of the tile across the atoms
 def test_resident_frames_and_an_atom_list(crowd, n_sel):
     """An atom's result from a host array and from the resident frames with an atom list that is not contiguous, the
     atoms that are not selected holding NaN: bit-equal, and the context stays as it was."""
@@ -259,6 +259,54 @@ def test_resident_frames_and_an_atom_list(crowd, n_sel):
         assert same(ctx.msd(positions=np.ascontiguousarray(holed[:, sel]), lags=lags, r4=True), ctx.msd(atoms=sel, lags=lags, r4=True))
         assert ctx.labels_version == version
         assert np.array_equal(resident_frames(ctx), holed, equal_nan=True)
+
+
+def bitwise(a, b):
+    return all((x is None and y is None) or (x.shape == y.shape and x.tobytes() == y.tobytes()) for x, y in zip(a, b))
+
+
+@pytest.mark.parametrize("F", [2, 33, 34])
+def test_an_atom_list_in_any_order(F):
+    """Resident frames and an atom list that descends and names one atom twice - 5 columns out of 40, the others holding
+    NaN - at the edges of the tile along the frames: bit for bit what the host array ``traj[:, list]`` gives, on both
+    paths, and the images are the restatement's."""
+    cell = Context.resident_cell()
+    wrapped, _, _ = wrapped_walk(F, 40, 80 + F, cell, drift=DRIFT)
+    sel = np.array([37, 30, 30, 12, 3])
+    mask = np.zeros(40, dtype=bool)
+    mask[sel] = True
+    holed = np.where(mask[None, :, None], wrapped, np.nan)
+    pos = np.ascontiguousarray(holed[:, sel])
+    _, images_ref, res_ref = R.unwrap(pos, cell)
+    lags = [0, 1, F - 1]
+    with Context(frames=holed) as ctx:
+        host = ctx.msd(positions=pos, max_lag=F - 1, collective=True, images=True)
+        res = ctx.msd(atoms=sel, max_lag=F - 1, collective=True, images=True)
+        host_d = ctx.msd(positions=pos, lags=lags, r4=True, collective=True, images=True)
+        res_d = ctx.msd(atoms=sel, lags=lags, r4=True, collective=True, images=True)
+    assert bitwise(host[:4], res[:4]) and host[4] == res[4] == res_ref
+    assert bitwise(host_d[:4], res_d[:4]) and host_d[4] == res_d[4] == res_ref
+    assert np.array_equal(res[3], images_ref) and np.array_equal(res_d[3], images_ref)
+    assert res[0][1].tobytes() == res[0][2].tobytes() and np.all(np.isfinite(res[0])) and np.all(np.isfinite(res[2]))
+    check_all_lags(R.series(pos, cell), res[0])
+
+
+@pytest.mark.parametrize("F", [33, 1025])
+def test_spectrum_and_msd_take_turns_on_one_context(F):
+    """The two operators share the pass kernel's table of roots and pad to different lengths here (64 and 128 points at
+    F = 33, 2048 and 4096 at F = 1025): a spectrum after an MSD is the spectrum before it, bit for bit, and each is right."""
+    from tests import vibfreq_ref as V
+    from tests.test_gpu_vibfreq import check_against_numpy
+    traj = R.random_walk(F, 3, seed=90 + F)
+    freqs, fmask = V.band(F - 1)
+    with Context(R.TRICLINIC) as ctx:
+        first = ctx.speed_spectrum(freqs, fmask, positions=traj, spectrum=True, speeds=True)
+        msd = ctx.msd(positions=traj, max_lag=F - 1)
+        third = ctx.speed_spectrum(freqs, fmask, positions=traj, spectrum=True, speeds=True)
+        again = ctx.msd(positions=traj, max_lag=F - 1)
+    assert bitwise(first, third) and bitwise(msd[:1], again[:1])
+    check_against_numpy(V.restatement(traj, slice(None)), *first)
+    check_all_lags(R.series(traj, R.TRICLINIC), msd[0])
 
 
 def test_nan_stays_with_its_atom(crowd):

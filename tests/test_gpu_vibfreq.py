@@ -144,7 +144,7 @@ def crowd():
     return traj, np.random.default_rng(22).permutation(140)
 
 
-@pytest.mark.parametrize("n_sel", [1, 2, 3, 65, 130])
+@pytest.mark.parametrize("n_sel", [1, 2, 3, 31, 32, 33, 65, 130])     # 31, 32, 33: the edges of the tile across the atoms
 def test_atoms(crowd, n_sel):
     traj, order = crowd
     sel = np.sort(order[:n_sel])                                 # not contiguous
@@ -162,6 +162,31 @@ def test_atoms(crowd, n_sel):
             assert np.array_equal(a, b)                          # resident frames + atom list: bit-identical
         assert ctx.labels_version == version
         assert np.array_equal(resident_frames(ctx), holed, equal_nan=True)
+
+
+@pytest.mark.parametrize("F", [2, 33, 34])
+def test_an_atom_list_in_any_order(F):
+    """Resident frames and an atom list that descends and names one atom twice - 5 columns out of 40, the others holding
+    NaN - at the edges of the tile along the frames (n = 1, 32, 33): bit for bit what the host array ``traj[:, list]``
+    gives, and the speeds are numpy's.  With n = 1 the band is empty: avg is 0 / 0 on either way."""
+    traj = V.random_walk(F, 40, seed=60 + F)
+    sel = np.array([37, 30, 30, 12, 3])
+    mask = np.zeros(40, dtype=bool)
+    mask[sel] = True
+    holed = np.where(mask[None, :, None], traj, np.nan)
+    d = traj[1:, sel] - traj[:-1, sel]
+    dx, dy, dz = d[..., 0], d[..., 1], d[..., 2]
+    expect = np.ascontiguousarray(np.sqrt((dx * dx + dy * dy) + dz * dz).T)
+    freqs, fmask = V.band(F - 1)
+    with Context(holed) as ctx:
+        host = ctx.speed_spectrum(freqs, fmask, positions=np.ascontiguousarray(holed[:, sel]), spectrum=True, speeds=True)
+        res = ctx.speed_spectrum(freqs, fmask, atoms=sel, spectrum=True, speeds=True)
+    for a, b in zip(host, res):
+        assert a.shape == b.shape and a.tobytes() == b.tobytes()
+    assert res[3].shape == (5, F - 1) and res[3].tobytes() == expect.tobytes()
+    assert res[2][1].tobytes() == res[2][2].tobytes() and np.all(np.isfinite(res[2]))     # the atom named twice
+    if F > 2:
+        np.testing.assert_allclose(res[0], V.restatement(traj, sel)["avg"], rtol=AVG_RTOL, atol=0)
 
 
 def test_nan_stays_with_its_atom(crowd):

@@ -19,7 +19,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 #   mode 1: float64 y[N]                                               -> float64 P[N + 1]; int64 chunks     (the squares)
 #   mode 2: int32 shift[N]                                             -> int32 sums[N]; int64 chunks
 #   mode 3: (K lags) float64 inv_m, P[N + 1], re[K]                    -> float64 s1[K], msd[K]
-#   mode 4: int64 n_sel, direct, collective, cap, stage_bits (N = F, K = n_lags) -> int64 out[10]
+#   mode 4: int64 n_sel, direct, collective, cap, stage_bits (N = F, K = n_lags) -> int64 out[11]
+#           out[10]: msd_layout() for batches of one atom, of atoms_per_batch and of the ragged last batch, on a null base and
+#           on a made-up one - 0, or the sum of 1 (the buffer is not head + fixed_bytes + B atom_bytes in both runs), 2 (a
+#           piece is not 16-byte aligned), 4 (a piece begins before the bytes the kernels touch of the piece before it end,
+#           or ends beyond the buffer)
 #   mode 5: float64 cm[9], ci[9], x[N, 3]; int32 n[N, 3]               -> float64 unwrapped[N, 3], frac[N, 3]
 PROBE = r"""
 #include <stdio.h>
@@ -58,6 +62,29 @@ template <typename T, class Load> static void scan(int64_t F, Load load, std::ve
         const int64_t c = e / MSD_CHUNK, j = (e % MSD_CHUNK) / MSD_GROUP;
         out[(size_t)e] = msd_scan_value(offsets[(size_t)c], before[(size_t)(c * MSD_THREADS + j)], local[(size_t)e]);
     }
+}
+
+static int layout_of(const MsdPlan &p, const MsdPlanIn &in, int64_t B)
+{
+    Carve sized = {nullptr, 0}, cv = {(char *)((uintptr_t)1 << 40), 0};
+    msd_layout(sized, p, in, B);
+    const MsdPieces w = msd_layout(cv, p, in, B);
+    const int64_t S = 3 * B, F = in.F, M = in.direct ? 0 : p.sp.M;
+    const struct { const void *at; int64_t bytes; } piece[] = {
+        {w.status, 8}, {w.atoms, in.n_sel * 8}, {w.lags, in.direct ? in.n_lags * 8 : 0}, {w.coll_y, in.collective ? 3 * F * 8 : 0},
+        {w.y, S * F * 8}, {w.images, S * F * 4}, {w.psum, in.direct ? 0 : S * (F + 1) * 8}, {w.totals, S * p.n_chunks * 8},
+        {w.buf, S * M * 16}, {w.out, S * in.n_lags * 8}, {w.r4, in.direct ? B * in.n_lags * 8 : 0}};
+    int bad = 0;
+    if (sized.used != cv.used || cv.used != w.head + p.fixed_bytes + B * p.atom_bytes || w.head % 256) bad |= 1;
+    int64_t end = 0;
+    for (const auto &q : piece) {
+        const int64_t off = (int64_t)((uintptr_t)q.at - (uintptr_t)cv.base);
+        if (off % 16) bad |= 2;
+        if (off < end) bad |= 4;
+        end = off + q.bytes;
+    }
+    if (end > cv.used || w.head != (int64_t)((uintptr_t)w.coll_y - (uintptr_t)cv.base)) bad |= 4;
+    return bad;
 }
 
 int main()
@@ -115,9 +142,14 @@ int main()
         SpKnobs k;
         k.workspace = SP_DEFAULT_WORKSPACE; k.stage_bits = (int)a[4]; k.lines = SP_MAX_LINES;
         const MsdPlan p = msd_plan(in, k);
-        const int64_t out[10] = {p.err ? 1 : 0, p.atoms_per_batch, p.n_batches, p.atom_bytes, p.fixed_bytes, p.workspace, p.n_chunks,
-                                 in.direct ? 0 : p.sp.M, in.direct ? 0 : p.sp.npass, MSD_MAX_BATCH};
-        wr(out, 8, 10);
+        int64_t layout = 0;
+        if (!p.err) {
+            const int64_t last = in.n_sel > 0 ? in.n_sel - (p.n_batches - 1) * p.atoms_per_batch : 1;
+            layout = layout_of(p, in, 1) | layout_of(p, in, p.atoms_per_batch) | layout_of(p, in, last);
+        }
+        const int64_t out[11] = {p.err ? 1 : 0, p.atoms_per_batch, p.n_batches, p.atom_bytes, p.fixed_bytes, p.workspace, p.n_chunks,
+                                 in.direct ? 0 : p.sp.M, in.direct ? 0 : p.sp.npass, MSD_MAX_BATCH, layout};
+        wr(out, 8, 11);
         return 0;
     }
     if (mode == 5) {
@@ -222,8 +254,11 @@ def test_windowed_term_and_combination(probe):
 
 def plan(probe, F, n_lags, n_sel, direct, collective, cap, stage_bits=10):
     out = np.frombuffer(probe(4, F, n_lags, np.array([n_sel, int(direct), int(collective), cap, stage_bits], dtype=np.int64)), dtype=np.int64)
-    keys = ["err", "atoms_per_batch", "n_batches", "atom_bytes", "fixed_bytes", "workspace", "n_chunks", "M", "npass", "max_batch"]
-    return dict(zip(keys, (int(v) for v in out)))
+    keys = ["err", "atoms_per_batch", "n_batches", "atom_bytes", "fixed_bytes", "workspace", "n_chunks", "M", "npass", "max_batch",
+            "layout"]
+    p = dict(zip(keys, (int(v) for v in out)))
+    assert len(out) == len(keys) and p["layout"] == 0             # the pieces of msd_layout: the plan's bytes, aligned, apart
+    return p
 
 
 @pytest.mark.parametrize("F,n_lags,direct", [(2, 2, False), (257, 129, False), (513, 513, False), (20000, 10001, False),

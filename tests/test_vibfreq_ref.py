@@ -44,10 +44,40 @@ def test_restatement_does_not_touch_its_input():
 
 # ---- the planner ----------------------------------------------------------------------------------------------------
 
-# One case per input line: n n_sel workspace_bytes want_spectrum; one output line: the plan.
+# One case per input line: n n_sel workspace_bytes want_spectrum; one output line: the plan.  `layout`: sp_layout() for
+# batches of one atom, of atoms_per_batch and of the ragged last batch, on a null base and on a made-up one - 0, or the sum
+# of 1 (the two runs size the buffer differently, or beyond head + workspace), 2 (a piece is not 16-byte aligned), 4 (a
+# piece begins before the bytes the kernels touch of the piece before it end, or ends beyond the buffer), 8 (atom_bytes is
+# not what a batch of one takes, in units of 256 bytes).
 PROBE = r"""
 #include <stdio.h>
 #include "spectrum_plan.h"
+
+static int layout_of(const SpPlan &p, const SpPlanIn &in, long long B)
+{
+    Carve sized = {nullptr, 0}, cv = {(char *)((uintptr_t)1 << 40), 0};
+    sp_layout(sized, p, in, B);
+    const SpPieces w = sp_layout(cv, p, in, B);
+    const long long tiles = p.pass[0].tiles;
+    const struct { const void *at; long long bytes; } piece[] = {
+        {w.freqs, p.nbins * 8}, {w.fmask, p.nbins}, {w.atoms, in.n_sel * 8}, {w.buf, B * p.M * 16}, {w.spec, B * p.nbins * 16},
+        {w.partial, B * tiles * 16}, {w.result, B * 16}, {w.speeds, B * in.n * 8}};
+    int bad = 0;
+    if (sized.used != cv.used || cv.used - w.head > p.workspace || w.head % 256) bad |= 1;
+    if (B == 1 && (cv.used - w.head + 255) / 256 * 256 != p.atom_bytes) bad |= 8;
+    if (in.want_spectrum != (w.spec != nullptr)) bad |= 4;
+    long long end = 0;
+    for (const auto &q : piece) {
+        if (!q.at) continue;
+        const long long off = (long long)((uintptr_t)q.at - (uintptr_t)cv.base);
+        if (off % 16) bad |= 2;
+        if (off < end) bad |= 4;
+        end = off + q.bytes;
+    }
+    if (end > cv.used || w.head > (long long)((uintptr_t)w.buf - (uintptr_t)cv.base)) bad |= 4;
+    return bad;
+}
+
 int main()
 {
     long long n, n_sel, ws; int spec;
@@ -55,9 +85,10 @@ int main()
         SpPlanIn in; in.n = n; in.n_sel = n_sel; in.workspace_bytes = ws; in.want_spectrum = spec != 0;
         const SpPlan p = sp_plan(in, sp_knobs_from_env());
         if (p.err) { printf("error: %s\n", p.err); continue; }
-        printf("M %lld nbins %lld npass %d atom_bytes %lld batch %lld n_batches %lld workspace %lld passes",
+        const long long last = n_sel > 0 ? n_sel - (p.n_batches - 1) * p.atoms_per_batch : 1;
+        printf("M %lld nbins %lld npass %d atom_bytes %lld batch %lld n_batches %lld workspace %lld layout %d passes",
                (long long)p.M, (long long)p.nbins, p.npass, (long long)p.atom_bytes, (long long)p.atoms_per_batch,
-               (long long)p.n_batches, (long long)p.workspace);
+               (long long)p.n_batches, (long long)p.workspace, layout_of(p, in, 1) | layout_of(p, in, p.atoms_per_batch) | layout_of(p, in, last));
         for (int i = 0; i < p.npass; i++)
             printf(" %d:%lld:%lld:%d:%d:%lld:%zu", p.pass[i].bits, (long long)p.pass[i].L, (long long)p.pass[i].S, p.pass[i].lines,
                    p.pass[i].pad, (long long)p.pass[i].tiles, p.pass[i].lds);
@@ -74,7 +105,8 @@ def probe(tmp_path_factory):
     src = td / "probe.cpp"
     src.write_text(PROBE)
     exe = str(td / "probe")
-    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "sitator_amd", "csrc"), str(src), "-o", exe])
+    subprocess.check_call(["g++", "-std=c++17", "-Wall", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I", os.path.join(ROOT, "sitator_amd", "csrc"), str(src), "-o", exe])
 
     def run(cases, env=None):
         text = "".join("%d %d %d %d\n" % c for c in cases)
@@ -90,8 +122,8 @@ def parse(line):
     if line.startswith("error:"):
         return {"err": line[7:]}
     tok = line.split()
-    p = {tok[i]: int(tok[i + 1]) for i in range(0, 14, 2)}
-    p["passes"] = [dict(zip(("bits", "L", "S", "lines", "pad", "tiles", "lds"), (int(v) for v in t.split(":")))) for t in tok[15:]]
+    p = {tok[i]: int(tok[i + 1]) for i in range(0, 16, 2)}
+    p["passes"] = [dict(zip(("bits", "L", "S", "lines", "pad", "tiles", "lds"), (int(v) for v in t.split(":")))) for t in tok[17:]]
     p["err"] = None
     return p
 
@@ -114,6 +146,7 @@ def check_consistent(p, n, n_sel, cap):
         assert q["lds"] >= 8 * (2 * q["lines"] * (q["L"] + q["pad"]) + q["L"] + 2 * 256) - 8
     assert S == 1
     assert p["workspace"] == p["batch"] * p["atom_bytes"] <= cap
+    assert p["layout"] == 0                            # the pieces of sp_layout: within the workspace, aligned, apart
     assert p["atom_bytes"] >= M * 16 + n * 8
     assert p["batch"] >= 1 and p["n_batches"] == -(-n_sel // p["batch"])
     assert (p["n_batches"] - 1) * p["batch"] < n_sel <= p["n_batches"] * p["batch"]
