@@ -3,6 +3,7 @@
 There is no CPU fallback: if the library is missing, or a call fails, this module raises.
 """
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -19,8 +20,56 @@ _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int64)
 _i32p = C.POINTER(C.c_int32)
 _u8p = C.POINTER(C.c_uint8)
+_u64p = C.POINTER(C.c_uint64)
 _vp = C.c_void_p
 i64 = C.c_int64
+
+# the pointer type an array's dtype names (complex128: the library sees pairs of doubles)
+_POINTER_OF = {np.dtype(np.float64): _dp, np.dtype(np.complex128): _dp, np.dtype(np.int64): _ip, np.dtype(np.int32): _i32p,
+               np.dtype(np.uint8): _u8p, np.dtype(np.uint64): _u64p}
+
+
+def _ptr(a, T=None):
+    """The address of the array ``a`` as the pointer type its dtype names (``T``: as that type instead); ``None`` stays
+    ``None``.  The library is never handed the address of an array that is not C-contiguous or of another dtype."""
+    if a is None:
+        return None
+    assert a.flags.c_contiguous, "the library reads C-contiguous arrays"
+    T = T or _POINTER_OF.get(a.dtype)
+    if T is None:
+        raise TypeError("no pointer type for an array of %s" % a.dtype)
+    return a.ctypes.data_as(T)
+
+
+def _d(a):
+    assert a is None or a.dtype == np.float64
+    return _ptr(a)
+
+
+def _i(a):
+    assert a is None or a.dtype == np.int64
+    return _ptr(a)
+
+
+def _void(a):
+    return _ptr(a, _vp)
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _i64(a):
+    return np.ascontiguousarray(a, dtype=np.int64)
+
+
+def _i32(a):
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _opt(convert, a):
+    """``convert(a)`` of an optional array, ``None`` of none."""
+    return None if a is None else convert(a)
 
 
 class SitError(C.Structure):
@@ -79,10 +128,10 @@ SIGNATURES = {
     "sit_get_assignments": (C.c_int, [_vp, _ip, _dp, _ip]),
     "sit_count_zero_rows": (C.c_int, [_vp, _ip, _ip]),
     "sit_gram": (C.c_int, [_vp, _dp, _ip]),
-    "sit_gram_limbs": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), _ip]),
-    "sit_weighted_row_sums_limbs": (C.c_int, [_vp, C.c_int, i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "sit_gram_limbs": (C.c_int, [_vp, _u64p, _u64p, _ip]),
+    "sit_weighted_row_sums_limbs": (C.c_int, [_vp, C.c_int, i64, _u64p, _u64p]),
     "sit_best_match": (C.c_int, [_vp, _dp, _ip, _dp, _dp]),
-    "sit_best_match_groups": (C.c_int, [_vp, C.POINTER(C.c_int32), _dp, i64, _ip, _dp, _dp]),
+    "sit_best_match_groups": (C.c_int, [_vp, _i32p, _dp, i64, _ip, _dp, _dp]),
     "sit_weighted_row_sums": (C.c_int, [_vp, C.c_int, i64, _dp, _dp]),
     "sit_site_anchors": (C.c_int, [_vp, C.c_int, i64, _dp, _ip, _dp]),
     "sit_site_sums": (C.c_int, [_vp, C.c_int, i64, _dp, _dp]),
@@ -136,9 +185,9 @@ SIGNATURES = {
     "sit_comm_create": (C.c_int, [_vp, _u8p, C.c_int, C.c_int]),
     "sit_comm_destroy": (C.c_int, [_vp]),
     "sit_comm_info": (C.c_int, [_vp, _i32p]),
-    "sit_comm_allreduce": (C.c_int, [_vp, C.c_void_p, i64, C.c_int, C.c_int]),
-    "sit_comm_allgather": (C.c_int, [_vp, C.c_void_p, C.c_void_p, i64]),
-    "sit_comm_broadcast": (C.c_int, [_vp, C.c_void_p, i64, C.c_int]),
+    "sit_comm_allreduce": (C.c_int, [_vp, _vp, i64, C.c_int, C.c_int]),
+    "sit_comm_allgather": (C.c_int, [_vp, _vp, _vp, i64]),
+    "sit_comm_broadcast": (C.c_int, [_vp, _vp, i64, C.c_int]),
     "sit_comm_barrier": (C.c_int, [_vp]),
     "sit_comm_attach": (C.c_int, [_vp, _vp]),
     "sit_timers": (C.c_int, [_vp, _dp, C.c_int]),
@@ -178,7 +227,7 @@ def load():
 def comm_unique_id():
     """ncclGetUniqueId: 128 bytes that rank 0 makes and every rank of the job receives."""
     uid = np.zeros(128, dtype=np.uint8)
-    if load().sit_comm_unique_id(uid.ctypes.data_as(_u8p)) != 0:
+    if load().sit_comm_unique_id(_ptr(uid)) != 0:
         raise RuntimeError("sit_comm_unique_id failed (librccl.so not loadable?)")
     return uid.tobytes()
 
@@ -189,58 +238,65 @@ def device_count():
     return n.value
 
 
+def _plan(keys, call):
+    """``(status, {key: word})`` of a plan entry point that writes ``len(keys)`` int64 words through ``call(out_ptr)``."""
+    out = np.zeros(len(keys), dtype=np.int64)
+    rc = call(_i(out))
+    return rc, {k: int(v) for k, v in zip(keys, out)}
+
+
+def _translations(plan):
+    return plan.pop("n0"), plan.pop("n1"), plan.pop("n2")
+
+
 def group_plan(n_entries, K):
     """``(entries per chunk, chunks, LDS form, largest K of the LDS form)`` of ``group_by_site`` (``sit_group_plan``)."""
-    out = np.zeros(4, dtype=np.int64)
-    if load().sit_group_plan(int(n_entries), int(K), _i(out)) != OK:
+    rc, plan = _plan(["per_chunk", "chunks", "lds", "lds_max_k"], lambda out: load().sit_group_plan(int(n_entries), int(K), out))
+    if rc != OK:
         raise ValueError("group_plan: beyond the capacity of group_by_site")
-    return int(out[0]), int(out[1]), bool(out[2]), int(out[3])
+    return plan["per_chunk"], plan["chunks"], bool(plan["lds"]), plan["lds_max_k"]
 
 
 def hull_plan():
     """``(facet capacity, open-edge capacity, threads per workgroup, LDS bytes per workgroup)`` of ``grouped_hull_volumes``
     (``sit_hull_plan``)."""
-    out = np.zeros(4, dtype=np.int64)
-    load().sit_hull_plan(_i(out))
-    return tuple(int(v) for v in out)
+    return tuple(_plan(["facets", "edges", "threads", "lds_bytes"], lambda out: load().sit_hull_plan(out))[1].values())
 
 
 def barrier_plan(cell, rc):
     """``{"translations": (n0, n1, n2), "tile": static atoms per LDS tile, "threads": per workgroup, "lds_bytes": per workgroup}``
     of ``barrier_energies`` for ``cell`` (rows are the cell vectors) and the cutoff ``rc`` (``sit_barrier_plan``)."""
-    out = np.zeros(6, dtype=np.int64)
     cell = _f64(cell).reshape(3, 3)
-    if load().sit_barrier_plan(_d(cell), float(rc), _i(out)) != OK:
+    status, plan = _plan(["n0", "n1", "n2", "tile", "threads", "lds_bytes"],
+                         lambda out: load().sit_barrier_plan(_d(cell), float(rc), out))
+    if status != OK:
         raise ValueError("barrier_plan: a degenerate cell, or rc not positive or beyond 255 perpendicular heights of the cell")
-    return {"translations": tuple(int(v) for v in out[:3]), "tile": int(out[3]), "threads": int(out[4]), "lds_bytes": int(out[5])}
+    plan["translations"] = _translations(plan)
+    return plan
 
 
 def soap_plan(cell, cutoff, n_species, n_max, l_max):
     """The plan of ``soap_vectors`` / ``soap_site_averages`` for ``cell`` (rows are the cell vectors) (``sit_soap_plan``): the
     translations, the workgroup, the neighbours staged at once, the LDS bytes, the limits and the lengths of a vector.  Beyond a
     limit: ``RuntimeError``."""
-    out = np.zeros(12, dtype=np.int64)
     cell = _f64(cell).reshape(3, 3)
-    rc = load().sit_soap_plan(_d(cell), float(cutoff), int(n_species), int(n_max), int(l_max), _i(out))
-    limits = {"max_l": int(out[6]), "max_n": int(out[7]), "max_species": int(out[8])}
+    keys = ["n0", "n1", "n2", "threads", "nbr_cap", "lds_bytes", "max_l", "max_n", "max_species", "n_coef", "n_dim", "n_dim_crossover"]
+    rc, plan = _plan(keys, lambda out: load().sit_soap_plan(_d(cell), float(cutoff), int(n_species), int(n_max), int(l_max), out))
     if rc == E_CAPACITY:
-        raise RuntimeError("soap_plan: l_max, n_max or the number of environment species is beyond %r" % limits)
+        raise RuntimeError("soap_plan: l_max, n_max or the number of environment species is beyond %r"
+                           % {k: plan[k] for k in ("max_l", "max_n", "max_species")})
     if rc != OK:
         raise ValueError("soap_plan: a degenerate cell, or a cutoff not positive or beyond 255 perpendicular heights of the cell")
-    plan = {"translations": tuple(int(v) for v in out[:3]), "threads": int(out[3]), "nbr_cap": int(out[4]), "lds_bytes": int(out[5]),
-            "n_coef": int(out[9]), "n_dim": int(out[10]), "n_dim_crossover": int(out[11])}
-    plan.update(limits)
+    plan["translations"] = _translations(plan)
     return plan
 
 
 def dpc_plan(d=1):
     """The plan of ``dpc_graph`` for points of ``d`` coordinates (``sit_dpc_plan``): the workgroup, the tile, the digits and passes
     of the radix select, the limits and the LDS bytes.  Beyond the largest ``d``: ``RuntimeError``."""
-    out = np.zeros(12, dtype=np.int64)
-    rc = load().sit_dpc_plan(int(d), _i(out))
     keys = ["threads", "tile", "digit_bits", "passes", "max_d", "lds_bytes", "segments", "max_n", "pca_rows", "pca_edge", "pca_max_d",
             "pca_max_n"]
-    plan = {k: int(v) for k, v in zip(keys, out)}
+    rc, plan = _plan(keys, lambda out: load().sit_dpc_plan(int(d), out))
     if rc == E_CAPACITY:
         raise RuntimeError("dpc_plan: more than %d coordinates per point" % plan["max_d"])
     if rc != OK:
@@ -251,12 +307,12 @@ def dpc_plan(d=1):
 def voronoi_plan(cell, S):
     """The plan of ``voronoi_nodes`` for ``cell`` (rows are the cell vectors) and ``S`` atoms (``sit_voronoi_plan``): the caps, the
     workgroup, and the first search radius with its growth factor."""
-    out, rad = np.zeros(8, dtype=np.int64), np.zeros(2)
+    rad = np.zeros(2)
     cell = _f64(cell).reshape(3, 3)
-    if load().sit_voronoi_plan(_d(cell), int(S), _i(out), _d(rad)) != OK:
-        raise ValueError("voronoi_plan: a degenerate cell or no atom")
     keys = ["neighbour_cap", "record_cap", "member_cap", "threads", "lds_bytes", "max_rounds", "record_bytes", "inverse_shape_min"]
-    plan = {k: int(v) for k, v in zip(keys, out)}
+    rc, plan = _plan(keys, lambda out: load().sit_voronoi_plan(_d(cell), int(S), out, _d(rad)))
+    if rc != OK:
+        raise ValueError("voronoi_plan: a degenerate cell or no atom")
     plan["first_radius"], plan["growth"] = float(rad[0]), float(rad[1])
     return plan
 
@@ -267,11 +323,11 @@ COORDENV_SHAPES = ("S:1", "L:2", "TL:3", "T:4", "S:4", "T:5", "S:5", "O:6", "T:6
 def coordenv_plan():
     """The plan of ``coordination_environments`` (``sit_coordenv_plan``): the caps, the workgroup, and the shape library as
     ``"symbols"``, ``"shape_n"`` and ``"shapes"`` (a list of ``[n, 3]`` unit vertices)."""
-    out, sn, co = np.zeros(8, dtype=np.int64), np.zeros(len(COORDENV_SHAPES), dtype=np.int32), np.zeros((len(COORDENV_SHAPES), 8, 3))
-    if load().sit_coordenv_plan(_i(out), sn.ctypes.data_as(_i32p), _d(co)) != OK:
-        raise ValueError("coordenv_plan")
+    sn, co = np.zeros(len(COORDENV_SHAPES), dtype=np.int32), np.zeros((len(COORDENV_SHAPES), 8, 3))
     keys = ["neighbour_cap", "vertex_cap", "face_cap", "coordination_cap", "max_n", "threads", "lds_bytes", "n_shapes"]
-    plan = {k: int(v) for k, v in zip(keys, out)}
+    rc, plan = _plan(keys, lambda out: load().sit_coordenv_plan(out, _ptr(sn), _d(co)))
+    if rc != OK:
+        raise ValueError("coordenv_plan")
     assert plan["n_shapes"] == len(COORDENV_SHAPES)
     plan["symbols"], plan["shape_n"] = list(COORDENV_SHAPES), [int(v) for v in sn]
     plan["shapes"] = [co[s, :sn[s]].copy() for s in range(len(COORDENV_SHAPES))]
@@ -283,20 +339,20 @@ def release_cached_memory():
     load().sit_release_cached_memory()
 
 
-def _d(a):
-    return a.ctypes.data_as(_dp)
+_STAGES = ("fill", "fit", "predict", "gram", "site_centers", "occupancy", "h2d")     # slots 0-6 of a block of sit_timers
 
 
-def _i(a):
-    return a.ctypes.data_as(_ip)
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _i64(a):
-    return np.ascontiguousarray(a, dtype=np.int64)
+def _settling(fn):
+    """Deferred ``fill`` passes are collected before their output is read: a failed pass raises here (as the reference
+    raises from inside its frame loop, landmark/helpers.pyx:76-92,116-118), a pass that outgrew its row buffers is run
+    again at the rigorous width (``fill_result``).  Every method that reads rows or labels carries this decorator."""
+    @functools.wraps(fn)
+    def wrapper(self, *args, **kwargs):
+        if self._deferred:
+            rc, _, err = self.fill_result()
+            self._check(rc, err)
+        return fn(self, *args, **kwargs)
+    return wrapper
 
 
 class HipContext(object):
@@ -333,6 +389,12 @@ class HipContext(object):
             self.lib.sit_destroy(self._h)
             self._h = None
 
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
     def __del__(self):
         try:
             self.close()
@@ -350,13 +412,50 @@ class HipContext(object):
             # (the methods below collect deferred passes - and repeat one that outgrew its row buffers - before they
             # read its output: _settling)
             raise RuntimeError("libsitator_hip: a deferred fill asked to be repeated (SIT_RETRY); call fill_result()")
-        if rc == E_INVALID:
-            raise ValueError(self.message())
-        if rc == E_NOT_CONVERGED:
+        if rc in (E_INVALID, E_NOT_CONVERGED):
             raise ValueError(self.message())
         if rc in (E_HIP, E_CAPACITY):
             raise RuntimeError("libsitator_hip: %s" % self.message())
         raise errors.DeviceDomainError(rc, err.frame if err else -1, err.index if err else -1)
+
+    def _check_index(self, rc):
+        if rc == E_INVALID and self.message().startswith("index "):
+            raise IndexError(self.message())
+        self._check(rc)
+
+    def _labels_rewritten(self):
+        """Every call that rewrites the resident labels says so here (site_trajectory.py decides by it whose they are)."""
+        self.labels_version += 1
+        self.labels_digest = None
+
+    def _records(self, width, call):
+        """The int64 ``[n, width]`` records of ``call(cap, rec_ptr, n_byref)`` (which gives the status): asked for with room
+        for ``1 << 16`` and, where there are more, again with room for all ``n``."""
+        cap = 1 << 16
+        while True:
+            rec = np.empty((cap, width), dtype=np.int64)
+            n = i64(0)
+            self._check(call(cap, _i(rec), C.byref(n)))
+            if n.value <= cap:
+                return rec[:n.value]
+            cap = int(n.value)
+
+    def _frames(self, positions, A=None):
+        """``(positions, F, A)``: a host ``[F, A, 3]`` array (of ``A`` atoms where that is given), or else ``None`` and the
+        sizes of the resident frames."""
+        if positions is None:
+            return None, self.F, self.A
+        positions = _f64(positions)
+        assert positions.ndim == 3 and positions.shape[2] == 3 and A in (None, positions.shape[1])
+        return positions, positions.shape[0], positions.shape[1]
+
+    def _selection(self, positions, atoms):
+        """``(positions, idx, F, n_sel)``: a host ``[F, n_sel, 3]`` array, or ``atoms`` as columns of the resident frames."""
+        if positions is not None:
+            positions, F, n_sel = self._frames(positions)
+            return positions, None, F, n_sel
+        idx = _i64(atoms).reshape(-1)
+        return None, idx, self.F, len(idx)
 
     # -- PBCCalculator surface
     def wrap_points(self, pts):
@@ -366,19 +465,19 @@ class HipContext(object):
         return pts
 
     def distances(self, pt1, pts2):
-        pt1 = _f64(pt1)
-        pts2 = _f64(pts2)
+        pt1, pts2 = _f64(pt1), _f64(pts2)
         out = np.empty(len(pts2))
         self._check(self.lib.sit_distances(self._h, _d(pt1), _d(pts2), len(pts2), _d(out)))
         return out
 
     def average(self, pts, weights=None):
         pts = _f64(pts)
-        w = None if weights is None else _f64(weights)
+        w = _opt(_f64, weights)
         out = np.empty(3)
-        self._check(self.lib.sit_average(self._h, _d(pts), None if w is None else _d(w), len(pts), _d(out)))
+        self._check(self.lib.sit_average(self._h, _d(pts), _d(w), len(pts), _d(out)))
         return out
 
+    @_settling
     def min_image(self, ref, pts):
         """``(moved points [n, 3], codes int32 [n])``: every ``pts[p]`` moved to its periodic image nearest ``ref[p]`` and
         the reference's code ``100 i + 10 j + k`` of that image (``sit_min_image``)."""
@@ -386,7 +485,7 @@ class HipContext(object):
         pts = np.array(pts, dtype=np.float64).reshape(-1, 3)
         assert ref.shape == pts.shape
         code = np.zeros(len(pts), dtype=np.int32)
-        self._check(self.lib.sit_min_image(self._h, _d(ref), _d(pts), len(pts), code.ctypes.data_as(_i32p)))
+        self._check(self.lib.sit_min_image(self._h, _d(ref), _d(pts), len(pts), _ptr(code)))
         return pts, code
 
     def site_vertex_distances(self, centers, ref_static, verts):
@@ -398,9 +497,7 @@ class HipContext(object):
 
     # -- residency
     def set_basis(self, ref_static, verts, vert_dists, midpoint, steepness, static_threshold):
-        ref_static = _f64(ref_static)
-        verts = _i64(verts)
-        vert_dists = _f64(vert_dists)
+        ref_static, verts, vert_dists = _f64(ref_static), _i64(verts), _f64(vert_dists)
         self.S = len(ref_static)
         self.D, self.V = verts.shape
         self._check(self.lib.sit_set_basis(self._h, _d(ref_static), self.S, _i(verts), _d(vert_dists),
@@ -413,14 +510,17 @@ class HipContext(object):
         self._check(self.lib.sit_frames_device_ptr(self._h, C.byref(p)))
         return p.value
 
-    def set_frames(self, frames, static_idx, mobile_idx, frame0=0):
-        frames = _f64(frames)
-        static_idx = _i64(static_idx)
-        mobile_idx = _i64(mobile_idx)
+    def _take_frames(self, frames, static_idx, mobile_idx, frame0):
+        """The arrays of a trajectory as the library reads them; the context takes its sizes from them."""
+        frames, static_idx, mobile_idx = _f64(frames), _i64(static_idx), _i64(mobile_idx)
         self.F, self.A = frames.shape[0], frames.shape[1]
         self.M = len(mobile_idx)
         self.N = self.F * self.M
         self.frame0 = int(frame0)
+        return frames, static_idx, mobile_idx
+
+    def set_frames(self, frames, static_idx, mobile_idx, frame0=0):
+        frames, static_idx, mobile_idx = self._take_frames(frames, static_idx, mobile_idx, frame0)
         self._check(self.lib.sit_set_frames(self._h, _d(frames), self.F, self.A, _i(static_idx), len(static_idx),
                                             _i(mobile_idx), self.M, self.frame0))
 
@@ -428,16 +528,9 @@ class HipContext(object):
                         check_for_zeros, fit_threshold):
         """``set_frames`` + ``fill`` + the first pass of ``fit_centers`` with the upload overlapped
         (``sit_upload_fill_fit``).  Returns ``(rc, n_all_zero, err, fitted)``."""
-        frames = _f64(frames)
-        static_idx = _i64(static_idx)
-        mobile_idx = _i64(mobile_idx)
-        self.F, self.A = frames.shape[0], frames.shape[1]
-        self.M = len(mobile_idx)
-        self.N = self.F * self.M
-        self.frame0 = int(frame0)
+        frames, static_idx, mobile_idx = self._take_frames(frames, static_idx, mobile_idx, frame0)
         p = FillParams.make(dynamic_lattice_mapping, relaxed_lattice_checks, check_for_zeros, 1, 0, 1, 0.0)
-        nz = i64(0)
-        err = SitError()
+        nz, err = i64(0), SitError()
         fitted = C.c_int(0)
         self._deferred = 0
         rc = self.lib.sit_upload_fill_fit(self._h, _d(frames), self.F, self.A, _i(static_idx), len(static_idx),
@@ -458,11 +551,9 @@ class HipContext(object):
         ``fill_result()`` (or a later ``fill`` / ``synchronize``)."""
         p = FillParams.make(dynamic_lattice_mapping, relaxed_lattice_checks, check_for_zeros, store_rows, assign, 1,
                             predict_threshold, defer)
-        nz = i64(0)
-        err = SitError()
+        nz, err = i64(0), SitError()
         if assign:
-            self.labels_version += 1
-            self.labels_digest = None
+            self._labels_rewritten()
         self._last_fill = p
         rc = self.lib.sit_fill(self._h, C.byref(p), C.byref(nz), C.byref(err))
         self._deferred = self._deferred + 1 if (defer and rc == OK) else 0
@@ -471,8 +562,7 @@ class HipContext(object):
     def fill_result(self):
         """Status, ``n_all_zero`` and error of the deferred passes in flight (waits for them; the first failure wins).
         A pass whose rows outgrew the buffers measured on the leading frames (``SIT_RETRY``) is run again, blocking."""
-        nz = i64(0)
-        err = SitError()
+        nz, err = i64(0), SitError()
         rc = self.lib.sit_fill_result(self._h, C.byref(nz), C.byref(err))
         self._deferred = 0
         if rc == RETRY:
@@ -483,23 +573,22 @@ class HipContext(object):
 
     def static_seen(self, local_frame):
         seen = np.zeros(self.S, dtype=np.uint8)
-        self._check(self.lib.sit_static_seen(self._h, int(local_frame), seen.ctypes.data_as(_u8p)))
+        self._check(self.lib.sit_static_seen(self._h, int(local_frame), _ptr(seen)))
         return seen
 
+    @_settling
     def rows_dense(self, row0=0, nrows=None):
         nrows = self.N - row0 if nrows is None else nrows
         out = np.empty((nrows, self.D))
         self._check(self.lib.sit_get_rows_dense(self._h, int(row0), int(nrows), _d(out)))
         return out
 
+    @_settling
     def rows_sparse(self, row0=0, nrows=None):
         nrows = self.N - row0 if nrows is None else nrows
         W = self.row_width()
-        nnz = np.empty(nrows, dtype=np.int32)
-        idx = np.empty((W, nrows), dtype=np.int32)
-        val = np.empty((W, nrows))
-        self._check(self.lib.sit_get_rows_sparse(self._h, int(row0), int(nrows), nnz.ctypes.data_as(_i32p),
-                                                 idx.ctypes.data_as(_i32p), _d(val)))
+        nnz, idx, val = np.empty(nrows, dtype=np.int32), np.empty((W, nrows), dtype=np.int32), np.empty((W, nrows))
+        self._check(self.lib.sit_get_rows_sparse(self._h, int(row0), int(nrows), _ptr(nnz), _ptr(idx), _d(val)))
         return nnz, idx, val
 
     def set_rows_dense(self, X):
@@ -526,6 +615,7 @@ class HipContext(object):
             self._check(self.lib.sit_fit_get_state(self._h, _d(centers), _i(counts), C.byref(K)))
         return centers, counts
 
+    @_settling
     def fit_push_stored_rows(self, threshold):
         self._check(self.lib.sit_fit_push_stored_rows(self._h, float(threshold)))
 
@@ -534,6 +624,7 @@ class HipContext(object):
         weights = _i64(weights)
         self._check(self.lib.sit_fit_push_dense_rows(self._h, _d(rows), _i(weights), len(rows), float(threshold)))
 
+    @_settling
     def set_centers(self, matrix, normed):
         matrix = _f64(matrix).reshape(-1, self.D)
         self.K = len(matrix)
@@ -567,24 +658,21 @@ class HipContext(object):
                 return pf[1]["arrays"]
         return np.empty(self.N, dtype=np.int64), np.empty(self.N)
 
+    @_settling
     def predict(self, threshold, fetch=True):
-        self.labels_version += 1
-        self.labels_digest = None
+        self._labels_rewritten()
         counts = np.zeros(self.K, dtype=np.int64)
-        if fetch:
-            labels, confs = self._assignment_arrays()
-            self._check(self.lib.sit_predict(self._h, float(threshold), _i(labels), _d(confs), _i(counts)))
-            return labels, confs, counts
-        self._check(self.lib.sit_predict(self._h, float(threshold), None, None, _i(counts)))
-        return None, None, counts
+        labels, confs = self._assignment_arrays() if fetch else (None, None)
+        self._check(self.lib.sit_predict(self._h, float(threshold), _i(labels), _d(confs), _i(counts)))
+        return labels, confs, counts
 
+    @_settling
     def assignments(self):
-        labels = np.empty(self.N, dtype=np.int64)
-        confs = np.empty(self.N)
-        counts = np.zeros(self.K, dtype=np.int64)
+        labels, confs, counts = np.empty(self.N, dtype=np.int64), np.empty(self.N), np.zeros(self.K, dtype=np.int64)
         self._check(self.lib.sit_get_assignments(self._h, _i(labels), _d(confs), _i(counts)))
         return labels, confs, counts
 
+    @_settling
     def count_zero_rows(self):
         """(number of all-zero rows, index of the first one or -1)."""
         n, first = i64(0), i64(0)
@@ -592,70 +680,65 @@ class HipContext(object):
         return n.value, first.value
 
     # -- mcl support
+    @_settling
     def gram(self):
-        G = np.empty((self.D, self.D))
-        seen = np.empty(self.D, dtype=np.int64)
+        G, seen = np.empty((self.D, self.D)), np.empty(self.D, dtype=np.int64)
         self._check(self.lib.sit_gram(self._h, _d(G), _i(seen)))
         return G, seen
 
+    @_settling
     def gram_limbs(self):
         """The Gram matrix as exact integers (hi, lo) in units of 2^-80 (see ``exact_sum_across``), and ``seen``."""
-        hi = np.empty((self.D, self.D), dtype=np.uint64)
-        lo = np.empty((self.D, self.D), dtype=np.uint64)
+        hi, lo = np.empty((self.D, self.D), dtype=np.uint64), np.empty((self.D, self.D), dtype=np.uint64)
         seen = np.empty(self.D, dtype=np.int64)
-        u64p = C.POINTER(C.c_uint64)
-        self._check(self.lib.sit_gram_limbs(self._h, hi.ctypes.data_as(u64p), lo.ctypes.data_as(u64p), _i(seen)))
+        self._check(self.lib.sit_gram_limbs(self._h, _ptr(hi), _ptr(lo), _i(seen)))
         return hi, lo, seen
 
+    @_settling
     def weighted_row_sums_limbs(self, K, weighted=True):
         n = K * self.D + K
-        hi = np.empty(n, dtype=np.uint64)
-        lo = np.empty(n, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        self._check(self.lib.sit_weighted_row_sums_limbs(self._h, int(weighted), int(K), hi.ctypes.data_as(u64p),
-                                                         lo.ctypes.data_as(u64p)))
+        hi, lo = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint64)
+        self._check(self.lib.sit_weighted_row_sums_limbs(self._h, int(weighted), int(K), _ptr(hi), _ptr(lo)))
         return hi, lo
 
+    @_settling
     def best_match(self, c):
         c = _f64(c)
-        row = i64(0)
-        dot = C.c_double(0)
-        nrm = C.c_double(0)
+        row, dot, nrm = i64(0), C.c_double(0), C.c_double(0)
         self._check(self.lib.sit_best_match(self._h, _d(c), C.byref(row), C.byref(dot), C.byref(nrm)))
         return row.value, dot.value, nrm.value
 
+    @_settling
     def best_match_groups(self, group_of_dim, cvec, G):
         """``best_match`` for ``G`` centres with disjoint supports in one pass: (rows, dots, norms), each ``[G]``."""
-        grp = np.ascontiguousarray(group_of_dim, dtype=np.int32)
+        grp = _i32(group_of_dim)
         cvec = _f64(cvec)
         assert grp.shape == (self.D,) and cvec.shape == (self.D,)
-        rows = np.empty(G, dtype=np.int64)
-        dots = np.empty(G)
-        nrms = np.empty(G)
-        self._check(self.lib.sit_best_match_groups(self._h, grp.ctypes.data_as(C.POINTER(C.c_int32)), _d(cvec), G,
-                                                   _i(rows), _d(dots), _d(nrms)))
+        rows, dots, nrms = np.empty(G, dtype=np.int64), np.empty(G), np.empty(G)
+        self._check(self.lib.sit_best_match_groups(self._h, _ptr(grp), _d(cvec), G, _i(rows), _d(dots), _d(nrms)))
         return rows, dots, nrms
 
+    @_settling
     def weighted_row_sums(self, K, weighted=True):
-        sums = np.empty((K, self.D))
-        wsum = np.empty(K)
+        sums, wsum = np.empty((K, self.D)), np.empty(K)
         self._check(self.lib.sit_weighted_row_sums(self._h, int(weighted), int(K), _d(sums), _d(wsum)))
         return sums, wsum
 
     # -- site centres / occupancy
+    @_settling
     def site_anchors(self, K, weighted):
-        wmax = np.empty(K)
-        first = np.empty(K, dtype=np.int64)
-        pts = np.empty((K, 3))
+        wmax, first, pts = np.empty(K), np.empty(K, dtype=np.int64), np.empty((K, 3))
         self._check(self.lib.sit_site_anchors(self._h, int(weighted), int(K), _d(wmax), _i(first), _d(pts)))
         return wmax, first, pts
 
+    @_settling
     def site_sums(self, K, weighted, anchors):
         anchors = _f64(anchors)
         sums = np.empty((K, 4))
         self._check(self.lib.sit_site_sums(self._h, int(weighted), int(K), _d(anchors), _d(sums)))
         return sums
 
+    @_settling
     def check_occupancy(self, K, max_per_site):
         a, b, c = i64(0), i64(0), i64(0)
         err = SitError()
@@ -664,84 +747,76 @@ class HipContext(object):
         return rc, a.value, b.value, c.value, err
 
     def set_assignments(self, labels, confs=None, frame0=0):
-        self.labels_version += 1
-        self.labels_digest = None
+        self._labels_rewritten()
         labels = _i64(labels)
         F, M = labels.shape
-        c = None if confs is None else _f64(confs)
-        self._check(self.lib.sit_set_assignments(self._h, _i(labels), None if c is None else _d(c), F, M, int(frame0)))
+        c = _opt(_f64, confs)
+        self._check(self.lib.sit_set_assignments(self._h, _i(labels), _d(c), F, M, int(frame0)))
         self.F, self.M, self.N, self.frame0 = F, M, F * M, int(frame0)
 
+    @_settling
     def site_counts(self, K):
         counts = np.zeros(int(K), dtype=np.int64)
         self._check(self.lib.sit_site_counts(self._h, int(K), _i(counts)))
         return counts
 
+    @_settling
     def cooccupancy(self, K):
         """``bool[K, K]``: entry (a, b) says whether some resident frame has one ion on site a and one on site b
         (``sit_cooccupancy``; at most 16384 sites)."""
         K = int(K)
         co = np.zeros((K, K), dtype=np.uint8)
-        rc = self.lib.sit_cooccupancy(self._h, K, co.ctypes.data_as(_u8p))
+        rc = self.lib.sit_cooccupancy(self._h, K, _ptr(co))
         # a label beyond the sites: the reference's connmat[site, frame] raises this (MergeSitesByThreshold.py:70)
         self._check_index(rc)
         return co.view(np.bool_)
 
     JUMP_NONE = -(1 << 63)
 
+    @_settling
     def jump_sources(self, unknown_as_jump=False, last_known_in=None):
-        src = np.empty((self.F, self.M), dtype=np.int64)
-        last_out = np.empty(self.M, dtype=np.int64)
-        lin = None if last_known_in is None else _i64(last_known_in)
-        self._check(self.lib.sit_jump_sources(self._h, int(unknown_as_jump), None if lin is None else _i(lin),
-                                              _i(src), _i(last_out)))
+        src, last_out = np.empty((self.F, self.M), dtype=np.int64), np.empty(self.M, dtype=np.int64)
+        lin = _opt(_i64, last_known_in)
+        self._check(self.lib.sit_jump_sources(self._h, int(unknown_as_jump), _i(lin), _i(src), _i(last_out)))
         return src, last_out
 
+    @_settling
     def jump_list(self, unknown_as_jump=False, last_known_in=None):
         """Jumps as an ``[n, 4]`` array of (frame, mobile atom, from site, to site), frame-major, and the last known
         site of every ion after this context's frames."""
         last_out = np.empty(self.M, dtype=np.int64)
-        lin = None if last_known_in is None else _i64(last_known_in)
-        cap = 1 << 16
-        while True:
-            rec = np.empty((cap, 4), dtype=np.int64)
-            n = i64(0)
-            self._check(self.lib.sit_jump_list(self._h, int(unknown_as_jump), None if lin is None else _i(lin), cap,
-                                               _i(rec), C.byref(n), _i(last_out)))
-            if n.value <= cap:
-                break
-            cap = int(n.value)
-        rec = rec[:n.value]
+        lin = _opt(_i64, last_known_in)
+        rec = self._records(4, lambda cap, rec, n: self.lib.sit_jump_list(self._h, int(unknown_as_jump), _i(lin), cap, rec, n,
+                                                                          _i(last_out)))
         order = np.lexsort((rec[:, 1], rec[:, 0]))
         return rec[order], last_out
 
+    @_settling
     def jump_analysis(self, K, last_known_in=None, time_at_current_in=None):
         n_ij = np.empty((K, K)); tsum = np.empty((K, K)); tn = np.empty((K, K), dtype=np.int64)
         total = np.empty(K, dtype=np.int64); nprob = i64(0)
         lout = np.empty(self.M, dtype=np.int64); tout = np.empty(self.M, dtype=np.int64)
-        lin = None if last_known_in is None else _i64(last_known_in)
-        tin = None if time_at_current_in is None else _i64(time_at_current_in)
-        rc = self.lib.sit_jump_analysis(self._h, int(K), None if lin is None else _i(lin),
-                                        None if tin is None else _i(tin), _d(n_ij), _d(tsum), _i(tn), _i(total),
+        lin = _opt(_i64, last_known_in)
+        tin = _opt(_i64, time_at_current_in)
+        rc = self.lib.sit_jump_analysis(self._h, int(K), _i(lin), _i(tin), _d(n_ij), _d(tsum), _i(tn), _i(total),
                                         C.byref(nprob), _i(lout), _i(tout))
         # a label beyond the site tables: the reference's fancy indexing raises this (dynamics/JumpAnalysis.py:75-88)
         self._check_index(rc)
         return n_ij, tsum, tn, total, nprob.value, lout, tout
 
+    @_settling
     def assign_last_known(self, frame_threshold, last_known_in=None, time_unknown_in=None, out=None):
         """``out``: a C-contiguous int64 [F, M] array that receives the new labels (else a fresh one)."""
         labels = np.empty((self.F, self.M), dtype=np.int64) if out is None else out
         assert labels.dtype == np.int64 and labels.flags.c_contiguous and labels.shape == (self.F, self.M)
-        self.labels_version += 1            # the kernel rewrites the resident labels in place
-        self.labels_digest = None
+        self._labels_rewritten()            # the kernel rewrites the resident labels in place
         fmax = np.zeros(max(self.F, 1), dtype=np.int32)
         st = np.zeros(3, dtype=np.int64)
         lout = np.empty(self.M, dtype=np.int64); tout = np.empty(self.M, dtype=np.int64)
-        lin = None if last_known_in is None else _i64(last_known_in)
-        tin = None if time_unknown_in is None else _i64(time_unknown_in)
-        self._check(self.lib.sit_assign_last_known(self._h, int(frame_threshold), None if lin is None else _i(lin),
-                                                   None if tin is None else _i(tin), _i(labels),
-                                                   fmax.ctypes.data_as(_i32p), _i(st), _i(lout), _i(tout)))
+        lin = _opt(_i64, last_known_in)
+        tin = _opt(_i64, time_unknown_in)
+        self._check(self.lib.sit_assign_last_known(self._h, int(frame_threshold), _i(lin), _i(tin), _i(labels), _ptr(fmax),
+                                                   _i(st), _i(lout), _i(tout)))
         return labels, fmax[:self.F], st, lout, tout
 
     # -- ReplaceUnassignedPositions: the resident labels are read, never written (labels_version stays)
@@ -756,6 +831,7 @@ class HipContext(object):
         assert b.shape == (self.M,) and a.shape == (self.M,)
         return b, a
 
+    @_settling
     def label_ends(self):
         """Per ion the first and the last label != -1 of this context's frames (``ENDS_NONE`` where it has none)."""
         first = np.full(self.M, self.ENDS_NONE, dtype=np.int64)
@@ -763,30 +839,25 @@ class HipContext(object):
         self._check(self.lib.sit_label_ends(self._h, _i(first), _i(last)))
         return first, last
 
+    @_settling
     def replace_unassigned(self, mode, before_in=None, after_in=None):
         """The labels with every -1 replaced by the nearest known label before it (``mode`` 0) or after it (1);
         ``before_in`` / ``after_in`` ([M]): what holds before the first and after the last frame (default -1)."""
         b, a = self._halo_pair(before_in, after_in)
         out = np.empty((self.F, self.M), dtype=np.int64)
-        self._check(self.lib.sit_replace_unassigned(self._h, int(mode), None if b is None else _i(b),
-                                                    None if a is None else _i(a), _i(out)))
+        self._check(self.lib.sit_replace_unassigned(self._h, int(mode), _i(b), _i(a), _i(out)))
         return out
 
+    @_settling
     def unknown_runs(self, before_in=None, after_in=None):
         """``(records, n_positions)``: every maximal run of -1 as (ion, start, end, before, after, pos_offset), ion-major
         and by start; start / end are global frame numbers (``sit_unknown_runs``)."""
         b, a = self._halo_pair(before_in, after_in)
-        cap = 1 << 16
-        while True:
-            rec = np.empty((cap, 6), dtype=np.int64)
-            n, npos = i64(0), i64(0)
-            self._check(self.lib.sit_unknown_runs(self._h, None if b is None else _i(b), None if a is None else _i(a),
-                                                  cap, _i(rec), C.byref(n), C.byref(npos)))
-            if n.value <= cap:
-                break
-            cap = int(n.value)
-        return rec[:n.value], int(npos.value)
+        npos = i64(0)
+        rec = self._records(6, lambda cap, rec, n: self.lib.sit_unknown_runs(self._h, _i(b), _i(a), cap, rec, n, C.byref(npos)))
+        return rec, int(npos.value)
 
+    @_settling
     def replace_closer(self, records, centers, positions):
         """The labels with the runs of ``records`` (as ``unknown_runs`` gives them) filled by the closer-site rule;
         ``positions`` [n_positions, 3]: the ion's real-space position at every frame of the runs with an offset.  A site
@@ -801,36 +872,27 @@ class HipContext(object):
         self._check_index(rc)
         return out
 
+    @_settling
     def running_mode(self, wleft, wright, threshold, replace_unknown, n_sites=0):
         """The smoothed labels, and (``n_sites`` > 0) how often every site occurs among them."""
         out = np.empty((self.F, self.M), dtype=np.int64)
         counts = np.zeros(int(n_sites), dtype=np.int64) if n_sites > 0 else None
         self._check(self.lib.sit_running_mode(self._h, int(wleft), int(wright), int(threshold), int(replace_unknown), _i(out),
-                                              int(n_sites), None if counts is None else _i(counts)))
+                                              int(n_sites), _i(counts)))
         return (out, counts) if counts is not None else out
 
     def recenter(self, arr, masses, factors, add3=None):
         assert arr.dtype == np.float64 and arr.flags.c_contiguous and arr.ndim == 3 and arr.shape[2] == 3
         masses = _f64(masses); factors = _f64(factors)
-        a3 = None if add3 is None else _f64(add3)
-        self._check(self.lib.sit_recenter(self._h, _d(arr), arr.shape[0], arr.shape[1], _d(masses), _d(factors),
-                                          None if a3 is None else _d(a3)))
+        a3 = _opt(_f64, add3)
+        self._check(self.lib.sit_recenter(self._h, _d(arr), arr.shape[0], arr.shape[1], _d(masses), _d(factors), _d(a3)))
 
     def recenter_resident(self, masses, factors, add3=None):
         """Recentre the frames resident after ``set_frames`` in place on the device (``sit_recenter_resident``)."""
         masses = _f64(masses); factors = _f64(factors)
         assert len(masses) == self.A and len(factors) == self.A
-        a3 = None if add3 is None else _f64(add3)
-        self._check(self.lib.sit_recenter_resident(self._h, _d(masses), _d(factors), None if a3 is None else _d(a3)))
-
-    def _selection(self, positions, atoms):
-        """``(positions, idx, F, n_sel)``: a host ``[F, n_sel, 3]`` array, or ``atoms`` as columns of the resident frames."""
-        if positions is not None:
-            positions = _f64(positions)
-            assert positions.ndim == 3 and positions.shape[2] == 3
-            return positions, None, positions.shape[0], positions.shape[1]
-        idx = _i64(atoms).reshape(-1)
-        return None, idx, self.F, len(idx)
+        a3 = _opt(_f64, add3)
+        self._check(self.lib.sit_recenter_resident(self._h, _d(masses), _d(factors), _d(a3)))
 
     # -- AverageVibrationalFrequency: reads frames only (labels_version, rows and labels stay)
     def speed_spectrum(self, freqs, fmask, positions=None, atoms=None, workspace_bytes=0, spectrum=False, speeds=False):
@@ -845,14 +907,11 @@ class HipContext(object):
         freqs = _f64(freqs)
         fmask = np.ascontiguousarray(fmask, dtype=np.uint8)
         assert freqs.shape == (nbins,) and fmask.shape == (nbins,)
-        avg = np.empty(n_sel)
-        power = np.empty(n_sel)
+        avg, power = np.empty(n_sel), np.empty(n_sel)
         spec = np.empty((n_sel, nbins), dtype=np.complex128) if spectrum else None
         spd = np.empty((n_sel, max(F - 1, 0))) if speeds else None
-        self._check(self.lib.sit_speed_spectrum(
-            self._h, None if positions is None else _d(positions), int(F), None if idx is None else _i(idx), int(n_sel),
-            _d(freqs), fmask.ctypes.data_as(_u8p), int(workspace_bytes), _d(avg), _d(power),
-            None if spec is None else spec.ctypes.data_as(_dp), None if spd is None else _d(spd)))
+        self._check(self.lib.sit_speed_spectrum(self._h, _d(positions), int(F), _i(idx), int(n_sel), _d(freqs), _ptr(fmask),
+                                                int(workspace_bytes), _d(avg), _d(power), _ptr(spec), _d(spd)))
         return avg, power, spec, spd
 
     # -- MeanSquaredDisplacement: reads frames only (labels_version, rows and labels stay)
@@ -880,15 +939,13 @@ class HipContext(object):
         coll = np.zeros((3, n_lags)) if collective else None
         img = np.zeros((n_sel, max(F, 0), 3), dtype=np.int32) if images else None
         res = C.c_double(0.0)
-        rc = self.lib.sit_msd(
-            self._h, None if positions is None else _d(positions), int(F), None if idx is None else _i(idx), int(n_sel),
-            int(bool(unwrap)), int(max_lag), None if lag_arr is None else _i(lag_arr), int(n_lags), int(bool(collective)),
-            int(workspace_bytes), _d(out), None if out4 is None else _d(out4), None if coll is None else _d(coll),
-            None if img is None else img.ctypes.data_as(_i32p), C.byref(res))
-        self._check(rc)
+        self._check(self.lib.sit_msd(self._h, _d(positions), int(F), _i(idx), int(n_sel), int(bool(unwrap)), int(max_lag), _i(lag_arr),
+                                     int(n_lags), int(bool(collective)), int(workspace_bytes), _d(out), _d(out4), _d(coll), _ptr(img),
+                                     C.byref(res)))
         return out, out4, coll, img, res.value
 
     # -- GenerateClampedTrajectory: reads labels and frames only (labels_version, rows and labels stay)
+    @_settling
     def clamp_trajectory(self, role, fixed_pos, centers, wrap, pass_through_unassigned, positions=None, workspace_bytes=0):
         """``float64[F, A, 3]`` (``sit_clamp_trajectory``): per atom, by ``role[a]``, its real position (-1),
         ``fixed_pos[a]`` (-2) or the centre of the site that column ``role[a]`` of the resident labels names - as given
@@ -898,22 +955,16 @@ class HipContext(object):
         of 1 GiB).  An unassigned label without ``pass_through_unassigned`` raises ``errors.UnassignedClampError`` (a
         ``RuntimeError``; ``.first_unassigned`` = the smallest frame * M + column), a label ``>= len(centers)``
         ``IndexError``, any other argument that does not fit the context ``ValueError``."""
-        role = np.ascontiguousarray(role, dtype=np.int32).reshape(-1)
+        role = _i32(role).reshape(-1)
         A = len(role)
         fixed_pos = _f64(fixed_pos).reshape(A, 3)
         centers = _f64(centers).reshape(-1, 3)
-        if positions is not None:
-            positions = _f64(positions)
-            assert positions.ndim == 3 and positions.shape[1:] == (A, 3)
-            F = positions.shape[0]
-        else:
-            F = self.F
+        positions, F, _ = self._frames(positions, A)
         out = np.empty((F, A, 3))
         first = i64(-1)
-        rc = self.lib.sit_clamp_trajectory(
-            self._h, None if positions is None else _d(positions), int(F), int(A), role.ctypes.data_as(_i32p), _d(fixed_pos),
-            _d(centers), len(centers), int(bool(wrap)), int(bool(pass_through_unassigned)), int(workspace_bytes), _d(out),
-            C.byref(first))
+        rc = self.lib.sit_clamp_trajectory(self._h, _d(positions), int(F), int(A), _ptr(role), _d(fixed_pos), _d(centers), len(centers),
+                                           int(bool(wrap)), int(bool(pass_through_unassigned)), int(workspace_bytes), _d(out),
+                                           C.byref(first))
         if rc == E_UNASSIGNED:
             raise errors.UnassignedClampError(first.value)
         # a label beyond the sites: the reference's centers_c[at_site] reads past the table (GenerateClampedTrajectory.pyx:99)
@@ -921,11 +972,7 @@ class HipContext(object):
         return out
 
     # -- per-site point clouds: reads labels and frames only (labels_version, rows and labels stay)
-    def _check_index(self, rc):
-        if rc == E_INVALID and self.message().startswith("index "):
-            raise IndexError(self.message())
-        self._check(rc)
-
+    @_settling
     def group_by_site(self, K, positions=None, mobile_idx=None, workspace_bytes=0):
         """``offsets`` int64 ``[K + 1]`` of a stable grouping of the assigned entries ``frame * M + column`` of the resident
         labels by site (``sit_group_by_site``): sites ascending, entries ascending inside a site - the order of
@@ -935,19 +982,15 @@ class HipContext(object):
         labels are rewritten.  A label ``>= K`` raises ``IndexError``, anything else that does not fit ``ValueError``."""
         K = int(K)
         offsets = np.zeros(K + 1, dtype=np.int64)
-        if positions is not None:
-            positions = _f64(positions)
-            assert positions.ndim == 3 and positions.shape[2] == 3
-            midx = _i64(mobile_idx).reshape(-1)
-            F, A, M = positions.shape[0], positions.shape[1], len(midx)
-        else:
-            midx = None
-            F, A, M = self.F, self.A, self.M
-        rc = self.lib.sit_group_by_site(self._h, None if positions is None else _d(positions), int(F), int(A),
-                                        None if midx is None else _i(midx), int(M), K, int(workspace_bytes), _i(offsets))
+        positions, F, A = self._frames(positions)
+        midx = _i64(mobile_idx).reshape(-1) if positions is not None else None
+        M = self.M if midx is None else len(midx)
+        rc = self.lib.sit_group_by_site(self._h, _d(positions), int(F), int(A), _i(midx), int(M), K, int(workspace_bytes),
+                                        _i(offsets))
         self._check_index(rc)
         return offsets
 
+    @_settling
     def grouped_fetch(self, first, n, points=True, confidences=False, entries=False):
         """``(points [n, 3], confidences [n], entries [n])`` of the elements ``[first, first + n)`` of the grouping, ``None``
         for what was not asked for.  ``ValueError`` ("stale ...") once the labels have been rewritten."""
@@ -955,10 +998,10 @@ class HipContext(object):
         pts = np.empty((n, 3)) if points else None
         cf = np.empty(n) if confidences else None
         en = np.empty(n, dtype=np.int64) if entries else None
-        self._check(self.lib.sit_grouped_fetch(self._h, int(first), n, None if pts is None else _d(pts),
-                                               None if cf is None else _d(cf), None if en is None else _i(en)))
+        self._check(self.lib.sit_grouped_fetch(self._h, int(first), n, _d(pts), _d(cf), _i(en)))
         return pts, cf, en
 
+    @_settling
     def grouped_bucket_averages(self, K, n_avg, weighted):
         """``(centers [K, n_avg, 3], anchors [K, n_avg])``: ``PBCCalculator.average`` of the elements of every site at ranks
         ``i, i + n_avg, ...`` (``sit_grouped_bucket_averages``); NaN / -1 for sites of at most ``n_avg`` elements."""
@@ -967,14 +1010,15 @@ class HipContext(object):
         self._check(self.lib.sit_grouped_bucket_averages(self._h, int(n_avg), int(bool(weighted)), _d(out), _i(anchors)))
         return out, anchors
 
+    @_settling
     def grouped_recenter_step(self, i, n_recenterings, out):
         """Step ``i`` of the cumulative recentring of every site's points (``sit_grouped_recenter_step``) into ``out``
         ``[N, 3]`` (float64, C-contiguous; ``None``: not copied back).  An empty site raises ``IndexError``."""
-        if out is not None:
-            assert out.dtype == np.float64 and out.flags.c_contiguous and out.ndim == 2 and out.shape[1] == 3
-        self._check_index(self.lib.sit_grouped_recenter_step(self._h, int(i), int(n_recenterings), None if out is None else _d(out)))
+        assert out is None or (out.ndim == 2 and out.shape[1] == 3)
+        self._check_index(self.lib.sit_grouped_recenter_step(self._h, int(i), int(n_recenterings), _d(out)))
         return out
 
+    @_settling
     def grouped_hull_volumes(self, K, vertex_mask=False):
         """``(volumes [K], status int32 [K], n_facets int32 [K], vertex_mask uint8 [N] or None)``: the convex hull of every
         site's points in the working copy as the last ``grouped_recenter_step`` left it (``sit_grouped_hull_volumes``).
@@ -984,14 +1028,12 @@ class HipContext(object):
         info = self.group_info()
         if int(K) != info["n_sites"]:
             raise ValueError("grouped_hull_volumes: K is not the number of sites of the grouping")
-        vols = np.empty(int(K))
-        status = np.empty(int(K), dtype=np.int32)
-        nf = np.empty(int(K), dtype=np.int32)
+        vols, status, nf = np.empty(int(K)), np.empty(int(K), dtype=np.int32), np.empty(int(K), dtype=np.int32)
         mask = np.zeros(info["n_grouped"], dtype=np.uint8) if vertex_mask else None
-        self._check(self.lib.sit_grouped_hull_volumes(self._h, _d(vols), status.ctypes.data_as(_i32p), nf.ctypes.data_as(_i32p),
-                                                      None if mask is None else mask.ctypes.data_as(_u8p)))
+        self._check(self.lib.sit_grouped_hull_volumes(self._h, _d(vols), _ptr(status), _ptr(nf), _ptr(mask)))
         return vols, status, nf, mask
 
+    @_settling
     def grouped_work_fetch(self, first, n):
         """``points [n, 3]`` of the elements ``[first, first + n)`` of the recentred working copy
         (``sit_grouped_work_fetch``)."""
@@ -1007,6 +1049,7 @@ class HipContext(object):
                 "bucket_avg_ms": float(v[5]), "recenter_ms": float(v[6]), "hull_ms": float(v[7])}
 
     # -- DiffusionPathwayAnalysis: reads nothing of the context but its cell
+    @_settling
     def pathway_components(self, conn, centers, n_images=27, codes=False):
         """``(root int32 [n_images * K], rounds, code int32 [K, K] or None)`` of the site graph ``conn`` ``[K, K]`` (non-zero:
         connected) under the context's cell (``sit_pathway_components``): per node ``image * K + site`` of the 3 x 3 x 3
@@ -1020,12 +1063,12 @@ class HipContext(object):
         root = np.empty(int(n_images) * K, dtype=np.int32)
         code = np.empty((K, K), dtype=np.int32) if codes else None
         rounds = i64(0)
-        self._check(self.lib.sit_pathway_components(self._h, K, conn.ctypes.data_as(_u8p), _d(centers), int(n_images),
-                                                    None if code is None else code.ctypes.data_as(_i32p),
-                                                    root.ctypes.data_as(_i32p), C.byref(rounds)))
+        self._check(self.lib.sit_pathway_components(self._h, K, _ptr(conn), _d(centers), int(n_images), _ptr(code), _ptr(root),
+                                                    C.byref(rounds)))
         return root, int(rounds.value), code
 
     # -- MergeSitesByBarrier: reads nothing of the context but its cell
+    @_settling
     def barrier_energies(self, static_pos, eps, sigma, rc, centers, pairs, coeffs, threshold, energies=True, codes=False):
         """``(energies [P, n] or None, verdict uint8 [P, 3], code int32 [P] or None)`` (``sit_barrier_energies``): per pair
         ``(i, j)`` of ``pairs`` ``[P, 2]`` the energy of one mobile atom at the ``n`` points ``vector * coeffs[m] + centers[i]``
@@ -1037,19 +1080,19 @@ class HipContext(object):
         eps, sigma = _f64(eps).reshape(-1), _f64(sigma).reshape(-1)
         assert len(eps) == len(static_pos) == len(sigma)
         centers = _f64(centers).reshape(-1, 3)
-        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        pairs = _i32(pairs).reshape(-1, 2)
         coeffs = _f64(coeffs).reshape(-1)
         P, n = len(pairs), len(coeffs)
         en = np.empty((P, n)) if energies else None
         verdict = np.zeros((P, 3), dtype=np.uint8)
         code = np.zeros(P, dtype=np.int32) if codes else None
-        self._check(self.lib.sit_barrier_energies(
-            self._h, _d(static_pos), _d(eps), _d(sigma), len(static_pos), float(rc), _d(centers), len(centers),
-            pairs.ctypes.data_as(_i32p), P, _d(coeffs), n, float(threshold), None if en is None else _d(en),
-            verdict.ctypes.data_as(_u8p), None if code is None else code.ctypes.data_as(_i32p)))
+        self._check(self.lib.sit_barrier_energies(self._h, _d(static_pos), _d(eps), _d(sigma), len(static_pos), float(rc), _d(centers),
+                                                  len(centers), _ptr(pairs), P, _d(coeffs), n, float(threshold), _d(en),
+                                                  _ptr(verdict), _ptr(code)))
         return en, verdict, code
 
     # -- VoronoiSiteGenerator: reads nothing of the context but its cell
+    @_settling
     def voronoi_nodes(self, static_pos, tau):
         """``{"centers" [n, 3], "radii" [n], "vertices" (list of n int arrays), "status" int32 [S], "nbr_count" int32 [S],
         "info" dict}`` (``sit_voronoi_nodes``, size call then fill call): the periodic Voronoi nodes of ``static_pos`` ``[S, 3]``
@@ -1060,13 +1103,13 @@ class HipContext(object):
         info = np.zeros(8)
         nn, ni = i64(0), i64(0)
         head = (self._h, _d(static_pos), S, float(tau))
-        tail = (status.ctypes.data_as(_i32p), nbr.ctypes.data_as(_i32p), _d(info))
+        tail = (_ptr(status), _ptr(nbr), _d(info))
         self._check(self.lib.sit_voronoi_nodes(*head, 0, 0, C.byref(nn), C.byref(ni), None, None, None, None, *tail))
         n, m = int(nn.value), int(ni.value)
         centers, radii = np.zeros((n, 3)), np.zeros(n)
         offsets, indices = np.zeros(n + 1, dtype=np.int64), np.zeros(max(m, 1), dtype=np.int32)
         self._check(self.lib.sit_voronoi_nodes(*head, n, m, C.byref(nn), C.byref(ni), _d(centers), _d(radii), _i(offsets),
-                                               indices.ctypes.data_as(_i32p), *tail))
+                                               _ptr(indices), *tail))
         assert int(nn.value) == n and int(ni.value) == m
         keys = ["rounds", "final_radius", "max_neighbours", "records", "kernel_ms", "first_radius", "merge_status"]
         out_info = {k: (float(v) if k in ("final_radius", "kernel_ms", "first_radius") else int(v)) for k, v in zip(keys, info)}
@@ -1074,6 +1117,7 @@ class HipContext(object):
                 "status": status, "nbr_count": nbr, "info": out_info}
 
     # -- SiteCoordinationEnvironment: reads nothing of the context but its cell
+    @_settling
     def coordination_environments(self, static_pos, centers, tau=1e-6, distance_cutoff=1.4, angle_cutoff=0.3, max_csm=8.0):
         """``{"status", "flags", "n", "shape" int32 [K], "vertices" (list of K int arrays: static indices of the coordinating
         images, ordered by distance, static index, image), "norm_distance", "norm_angle" (lists of K arrays), "csm_best" [K],
@@ -1086,15 +1130,15 @@ class HipContext(object):
         best, call, conf, info = np.zeros(max(K, 1)), np.zeros((max(K, 1), 3)), np.zeros(max(K, 1)), np.zeros(8)
         ni = i64(0)
         head = (self._h, _d(static_pos), S, _d(centers), K, float(tau), float(distance_cutoff), float(angle_cutoff), float(max_csm))
-        per = (status.ctypes.data_as(_i32p), flags.ctypes.data_as(_i32p), n.ctypes.data_as(_i32p))
-        tail = (shape.ctypes.data_as(_i32p), _d(best), _d(call), _d(conf), _d(info))
+        per = (_ptr(status), _ptr(flags), _ptr(n))
+        tail = (_ptr(shape), _d(best), _d(call), _d(conf), _d(info))
         self._check(self.lib.sit_coordination_environments(*head, 0, C.byref(ni), *per, None, None, None, None, *tail))
         computed = int(info[7])
         m = int(ni.value)
         offsets, indices = np.zeros(K + 1, dtype=np.int64), np.zeros(max(m, 1), dtype=np.int32)
         nd, na = np.zeros(max(m, 1)), np.zeros(max(m, 1))
-        self._check(self.lib.sit_coordination_environments(*head, m, C.byref(ni), *per, _i(offsets), indices.ctypes.data_as(_i32p), _d(nd),
-                                                           _d(na), *tail))
+        self._check(self.lib.sit_coordination_environments(*head, m, C.byref(ni), *per, _i(offsets), _ptr(indices), _d(nd), _d(na),
+                                                           *tail))
         assert int(ni.value) == m
         keys = ["rounds", "final_radius", "max_neighbours", "max_n", "cell_ms", "csm_ms", "first_radius", "fill_computed"]
         out_info = {k: (int(v) if k in ("rounds", "max_neighbours", "max_n", "fill_computed") else float(v)) for k, v in zip(keys, info)}
@@ -1105,52 +1149,48 @@ class HipContext(object):
 
     # -- SOAP descriptors: soap_vectors reads nothing of the context but its cell, soap_site_averages labels and frames only
     def _soap_args(self, soap):
-        """The tail of scalars and tables the SOAP entry points share, from a ``soap`` dict (``site_descriptors.soap_tables``), and
-        the arrays its pointers point into (the caller holds them for the duration of the call)."""
+        """The tail of scalars and tables the SOAP entry points share, from a ``soap`` dict (``site_descriptors.soap_tables``)."""
         alpha, beta = _f64(soap["alpha"]), _f64(soap["beta"])
         L, n = int(soap["l_max"]) + 1, int(soap["n_max"])
         assert alpha.shape == (L, n) and beta.shape == (L, n, n)
         return (float(soap["cutoff"]), float(soap["cutoff_transition_width"]), float(soap["atom_sigma"]), int(soap["n_species"]), n,
-                L - 1, int(bool(soap["crossover"])), _d(alpha), _d(beta), int(soap["n_dim"])), (alpha, beta)
+                L - 1, int(bool(soap["crossover"])), _d(alpha), _d(beta), int(soap["n_dim"]))
 
+    @_settling
     def soap_vectors(self, static_pos, species_idx, centers, soap, nbr_count=False):
         """``(out [P, n_dim], nbr_count int32 [P] or None)`` (``sit_soap_vectors``): the SOAP power spectrum of every centre among
         the atoms ``static_pos`` ``[S, 3]`` and all their periodic images under the context's cell; ``species_idx`` ``[S]``: the
         index of an atom's species in the environment list, -1 for an atom outside it.  ``soap``: the dict of
         ``site_descriptors.soap_tables``.  Beyond a capacity ``RuntimeError``, anything else that does not fit ``ValueError``."""
         static_pos = _f64(static_pos).reshape(-1, 3)
-        species_idx = np.ascontiguousarray(species_idx, dtype=np.int32).reshape(-1)
+        species_idx = _i32(species_idx).reshape(-1)
         assert len(species_idx) == len(static_pos)
         centers = _f64(centers).reshape(-1, 3)
-        tail, keep = self._soap_args(soap)
+        tail = self._soap_args(soap)
         P = len(centers)
         out = np.zeros((P, int(soap["n_dim"])))
         cnt = np.zeros(P, dtype=np.int32) if nbr_count else None
-        self._check(self.lib.sit_soap_vectors(self._h, _d(static_pos), species_idx.ctypes.data_as(_i32p), len(static_pos), _d(centers), P,
-                                              *tail, _d(out), None if cnt is None else cnt.ctypes.data_as(_i32p)))
+        self._check(self.lib.sit_soap_vectors(self._h, _d(static_pos), _ptr(species_idx), len(static_pos), _d(centers), P, *tail,
+                                              _d(out), _ptr(cnt)))
         return out, cnt
 
+    @_settling
     def soap_site_averages(self, K, static_idx, species_idx, mobile_idx, soap, stepsize=1, averaging=None, avg_descriptors_per_site=None,
                            positions=None, workspace_bytes=0):
         """``(descs [R, n_dim], counts [K], nr_of_descs [K], info)`` (``sit_soap_site_averages``, size call then fill call): the
         averaged SOAP vectors of ``SOAPDescriptorAverages`` on the resident labels; ``positions``: a host ``[F, A, 3]`` float64
         array, without it the frames resident after ``set_frames`` are read.  A label ``>= K`` raises ``IndexError``."""
         static_idx, mobile_idx = _i64(static_idx).reshape(-1), _i64(mobile_idx).reshape(-1)
-        species_idx = np.ascontiguousarray(species_idx, dtype=np.int32).reshape(-1)
+        species_idx = _i32(species_idx).reshape(-1)
         assert len(species_idx) == len(static_idx)
-        if positions is not None:
-            positions = _f64(positions)
-            assert positions.ndim == 3 and positions.shape[2] == 3
-            F, A = positions.shape[0], positions.shape[1]
-        else:
-            F, A = self.F, self.A
+        positions, F, A = self._frames(positions)
         K = int(K)
-        tail, keep = self._soap_args(soap)
+        tail = self._soap_args(soap)
         counts, nr = np.zeros(K, dtype=np.int64), np.zeros(K, dtype=np.int64)
         info = np.zeros(4)
         n_rows = i64(0)
-        head = (self._h, None if positions is None else _d(positions), int(F), int(A), _i(static_idx), species_idx.ctypes.data_as(_i32p),
-                len(static_idx), _i(mobile_idx), len(mobile_idx), K, int(stepsize), int(averaging or 0), int(avg_descriptors_per_site or 0))
+        head = (self._h, _d(positions), int(F), int(A), _i(static_idx), _ptr(species_idx), len(static_idx), _i(mobile_idx),
+                len(mobile_idx), K, int(stepsize), int(averaging or 0), int(avg_descriptors_per_site or 0))
         self._check_index(self.lib.sit_soap_site_averages(*head, *tail, int(workspace_bytes), 0, C.byref(n_rows), _i(counts), _i(nr),
                                                           None, _d(info)))
         R = int(n_rows.value)
@@ -1162,6 +1202,7 @@ class HipContext(object):
                                    "averaging": int(info[3])}
 
     # -- SiteTypeAnalysis: PCA statistics and density-peak clustering; they read nothing of the context but its device
+    @_settling
     def pca_covariance(self, X):
         """``(mean [D], cov [D, D])`` of the rows ``X`` ``[N, D]`` (``sit_pca_covariance``): ``cov`` has the divisor
         ``max(N - 1, 1)``.  Beyond a capacity ``RuntimeError``, anything else that does not fit ``ValueError``."""
@@ -1172,6 +1213,7 @@ class HipContext(object):
         self._check(self.lib.sit_pca_covariance(self._h, _d(X), N, D, _d(mean), _d(cov)))
         return mean, cov
 
+    @_settling
     def pca_project(self, X, mean, components):
         """``Y [N, d] = (X - mean) @ components.T`` for ``components`` ``[d, D]`` (``sit_pca_project``)."""
         X, mean, components = _f64(X), _f64(mean).reshape(-1), _f64(components)
@@ -1182,6 +1224,7 @@ class HipContext(object):
         self._check(self.lib.sit_pca_project(self._h, _d(X), N, D, _d(mean), _d(components), d, _d(Y)))
         return Y
 
+    @_settling
     def dpc_graph(self, Y, fraction=0.02):
         """``(kernel_size, density [N], delta [N], neighbour int32 [N], info)`` (``sit_dpc_graph``): what ``pydpc.Cluster(Y,
         fraction)`` computes for the points ``Y`` ``[N, d]``, by the definitions of ``csrc/dpc_plan.h``.  ``info``: the kernel
@@ -1191,16 +1234,17 @@ class HipContext(object):
         N, d = Y.shape
         ks = C.c_double(0.0)
         density, delta, nbr, info = np.zeros(N), np.zeros(N), np.zeros(N, dtype=np.int32), np.zeros(2)
-        self._check(self.lib.sit_dpc_graph(self._h, _d(Y), N, d, float(fraction), C.byref(ks), _d(density), _d(delta),
-                                           nbr.ctypes.data_as(_i32p), _d(info)))
+        self._check(self.lib.sit_dpc_graph(self._h, _d(Y), N, d, float(fraction), C.byref(ks), _d(density), _d(delta), _ptr(nbr),
+                                           _d(info)))
         return ks.value, density, delta, nbr, {"kernel_ms": float(info[0]), "pairs": int(info[1])}
 
+    @_settling
     def dpc_assign(self, density, delta, neighbour, min_density, min_delta, dvecs_to_site=None, K=0):
         """``(membership int32 [N], clusters int32 [n_clusters], votes int64 [K, n_clusters] or None)`` (``sit_dpc_assign``):
         centres are the points with ``density > min_density`` and ``delta > min_delta``, every other point follows its neighbour;
         ``votes[s, m]`` counts the points of site ``dvecs_to_site[i] == s`` with membership ``m``."""
         density, delta = _f64(density).reshape(-1), _f64(delta).reshape(-1)
-        neighbour = np.ascontiguousarray(neighbour, dtype=np.int32).reshape(-1)
+        neighbour = _i32(neighbour).reshape(-1)
         N = len(density)
         assert len(delta) == N == len(neighbour)
         K = int(K) if dvecs_to_site is not None else 0
@@ -1210,10 +1254,9 @@ class HipContext(object):
         nc = i64(0)
         guess = int(np.count_nonzero((density > min_density) & (delta > min_delta)))
         votes = np.zeros((K, guess), dtype=np.int64) if K > 0 else None
-        self._check(self.lib.sit_dpc_assign(self._h, _d(density), _d(delta), neighbour.ctypes.data_as(_i32p), N, float(min_density),
-                                            float(min_delta), None if site is None else _i(site), K,
-                                            membership.ctypes.data_as(_i32p), clusters.ctypes.data_as(_i32p), C.byref(nc),
-                                            None if votes is None else _i(votes), 0 if votes is None else votes.size))
+        self._check(self.lib.sit_dpc_assign(self._h, _d(density), _d(delta), _ptr(neighbour), N, float(min_density), float(min_delta),
+                                            _i(site), K, _ptr(membership), _ptr(clusters), C.byref(nc), _i(votes),
+                                            0 if votes is None else votes.size))
         assert int(nc.value) == guess
         return membership, clusters[:guess].copy(), votes
 
@@ -1221,7 +1264,7 @@ class HipContext(object):
     def comm_create(self, unique_id, rank, world):
         uid = np.frombuffer(bytes(unique_id), dtype=np.uint8).copy()
         assert uid.size == 128
-        self._check(self.lib.sit_comm_create(self._h, uid.ctypes.data_as(_u8p), int(rank), int(world)))
+        self._check(self.lib.sit_comm_create(self._h, _ptr(uid), int(rank), int(world)))
 
     def comm_destroy(self):
         self.lib.sit_comm_destroy(self._h)
@@ -1229,28 +1272,24 @@ class HipContext(object):
     def comm_info(self):
         """What the RCCL communicator reports about itself (``sit_comm_info``)."""
         v = np.zeros(6, dtype=np.int32)
-        self._check(self.lib.sit_comm_info(self._h, v.ctypes.data_as(_i32p)))
+        self._check(self.lib.sit_comm_info(self._h, _ptr(v)))
         return {"ranks": int(v[0]), "rank": int(v[1]), "device": int(v[2]), "rccl_version": int(v[3]),
                 "asked_ranks": int(v[4]), "asked_rank": int(v[5])}
 
     def comm_allreduce(self, arr, op="sum"):
         """In place on a contiguous float64 / int64 / uint64 array."""
         code = {np.dtype(np.float64): 0, np.dtype(np.int64): 1, np.dtype(np.uint64): 2}[arr.dtype]
-        assert arr.flags.c_contiguous
-        self._check(self.lib.sit_comm_allreduce(self._h, arr.ctypes.data_as(C.c_void_p), arr.size, code,
-                                                {"sum": 0, "min": 1, "max": 2}[op]))
+        self._check(self.lib.sit_comm_allreduce(self._h, _void(arr), arr.size, code, {"sum": 0, "min": 1, "max": 2}[op]))
         return arr
 
     def comm_allgather(self, send, world):
         send = np.ascontiguousarray(send)
         recv = np.empty((world,) + send.shape, dtype=send.dtype)
-        self._check(self.lib.sit_comm_allgather(self._h, send.ctypes.data_as(C.c_void_p), recv.ctypes.data_as(C.c_void_p),
-                                                send.nbytes))
+        self._check(self.lib.sit_comm_allgather(self._h, _void(send), _void(recv), send.nbytes))
         return recv
 
     def comm_broadcast(self, arr, root):
-        assert arr.flags.c_contiguous
-        self._check(self.lib.sit_comm_broadcast(self._h, arr.ctypes.data_as(C.c_void_p), arr.nbytes, int(root)))
+        self._check(self.lib.sit_comm_broadcast(self._h, _void(arr), arr.nbytes, int(root)))
         return arr
 
     def comm_barrier(self):
@@ -1261,23 +1300,25 @@ class HipContext(object):
         ``comm_ctx``'s communicator, reduced on the device (``sit_comm_attach``); ``None`` detaches."""
         self._check(self.lib.sit_comm_attach(self._h, comm_ctx._h if comm_ctx is not None else None))
 
+    def _timer_slots(self, n=24):
+        """The first ``n`` slots of ``sit_timers``: three blocks of 8 - the last lap of every stage in ms, the sum of all
+        its laps, their number; slots 0-6 of a block are ``_STAGES``, slot 7 the ``k_clamp`` launches."""
+        t = np.zeros(n)
+        self.lib.sit_timers(self._h, _d(t), n)
+        return t
+
     def timers(self):
-        t = np.zeros(8)
-        self.lib.sit_timers(self._h, _d(t), 8)
-        return dict(zip(["fill", "fit", "predict", "gram", "site_centers", "occupancy", "h2d"], t))
+        return dict(zip(_STAGES, self._timer_slots(8)))
 
     def timer_totals(self):
         """(sum of all laps in ms, number of laps) per stage since the context was made."""
-        t = np.zeros(24)
-        self.lib.sit_timers(self._h, _d(t), 24)
-        names = ["fill", "fit", "predict", "gram", "site_centers", "occupancy", "h2d"]
-        return {k: (float(t[8 + i]), int(t[16 + i])) for i, k in enumerate(names)}
+        t = self._timer_slots()
+        return {k: (float(t[8 + i]), int(t[16 + i])) for i, k in enumerate(_STAGES)}
 
     def clamp_kernel_time(self):
         """(sum in ms, number) of the ``k_clamp`` launches of ``clamp_trajectory`` since the context was made: the
         kernel alone, without the copies of a call (slot 7 of ``sit_timers``)."""
-        t = np.zeros(24)
-        self.lib.sit_timers(self._h, _d(t), 24)
+        t = self._timer_slots()
         return float(t[15]), int(t[23])
 
     def info(self):
@@ -1305,43 +1346,15 @@ class HipContext(object):
         ``off`` int32 [bins + 1], ``list`` int32 [total], ``crit`` uint8 [total].  ``ValueError`` when there is no such table."""
         G = np.zeros(3, dtype=np.int32)
         disp, rb, total = C.c_double(0), C.c_double(0), i64(0)
-        head = (self._h, int(which), G.ctypes.data_as(_i32p), C.byref(disp), C.byref(rb), C.byref(total))
+        head = (self._h, int(which), _ptr(G), C.byref(disp), C.byref(rb), C.byref(total))
         self._check(self.lib.sit_candidate_table(*head, 0, None, 0, None, None))
         nb, n = int(G[0]) * int(G[1]) * int(G[2]), int(total.value)
         off = np.zeros(nb + 1, dtype=np.int32)
         lst = np.zeros(max(n, 1), dtype=np.int32)
         crit = np.zeros(max(n, 1), dtype=np.uint8)
-        self._check(self.lib.sit_candidate_table(*head, nb + 1, off.ctypes.data_as(_i32p), len(lst), lst.ctypes.data_as(_i32p),
-                                                 crit.ctypes.data_as(_u8p)))
+        self._check(self.lib.sit_candidate_table(*head, nb + 1, _ptr(off), len(lst), _ptr(lst), _ptr(crit)))
         return {"grid": [int(x) for x in G], "displacement": disp.value, "rb": rb.value, "total": n, "off": off,
                 "list": lst[:n], "crit": crit[:n]}
 
     def synchronize(self):
         self._check(self.lib.sit_synchronize(self._h))
-
-
-def _settling(fn):
-    """Deferred ``fill`` passes are collected before their output is read: a failed pass raises here (as the reference
-    raises from inside its frame loop, landmark/helpers.pyx:76-92,116-118), a pass that outgrew its row buffers is run
-    again at the rigorous width (``fill_result``)."""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapper(self, *args, **kwargs):
-        if self._deferred:
-            rc, _, err = self.fill_result()
-            self._check(rc, err)
-        return fn(self, *args, **kwargs)
-    return wrapper
-
-
-for _name in ("rows_dense", "rows_sparse", "fit_push_stored_rows", "predict", "assignments", "count_zero_rows", "gram",
-              "gram_limbs", "weighted_row_sums", "weighted_row_sums_limbs", "best_match", "best_match_groups",
-              "site_anchors", "site_sums", "check_occupancy", "site_counts", "cooccupancy", "jump_sources", "jump_list",
-              "jump_analysis", "assign_last_known", "running_mode", "set_centers", "label_ends", "replace_unassigned",
-              "unknown_runs", "replace_closer", "clamp_trajectory", "group_by_site", "grouped_fetch", "grouped_bucket_averages",
-              "grouped_recenter_step", "grouped_hull_volumes", "grouped_work_fetch", "min_image", "pathway_components",
-              "barrier_energies", "voronoi_nodes", "coordination_environments", "soap_vectors", "soap_site_averages", "pca_covariance", "pca_project", "dpc_graph",
-              "dpc_assign"):
-    setattr(HipContext, _name, _settling(getattr(HipContext, _name)))
-del _name

@@ -20,6 +20,7 @@ device-resident site assignments:
   mean squared displacement against the lag, unwrapped under the cell on the device, also straight from the trajectory a
   ``LandmarkAnalysis`` left resident)
 """
+import contextlib
 import logging
 import operator
 
@@ -199,12 +200,11 @@ class SmoothSiteTrajectory(object):
         ext = np.concatenate(before + [lab] + after)
         nb = sum(len(b) for b in before)
         device = st._ctx.device if st._ctx is not None else None
-        scratch = _lib.HipContext(np.asarray(st.site_network.structure.cell, dtype=np.float64), device=device)
-        try:
+        # closing(): the scratch context needs no more than close() of whatever class makes it
+        cell = np.asarray(st.site_network.structure.cell, dtype=np.float64)
+        with contextlib.closing(_lib.HipContext(cell, device=device)) as scratch:
             scratch.set_assignments(ext)
             res = scratch.running_mode(wleft, wright, threshold, self.set_unassigned_under_threshold, n_sites=n_sites)
-        finally:
-            scratch.close()
         if n_sites == 0:
             return np.ascontiguousarray(res[nb:nb + n]), np.zeros(0, dtype=np.int64)
         out, counts = res
@@ -595,11 +595,8 @@ class AverageVibrationalFrequency(object):
         freqs, fmask = self._band(len(selected))
         if selected.shape[1] == 0:
             return self._over_atoms(np.empty(0), np.empty(0), return_stdev)
-        ctx = _lib.HipContext(np.eye(3))                           # no cell enters: the differences are not wrapped
-        try:
+        with _lib.HipContext(np.eye(3)) as ctx:                    # no cell enters: the differences are not wrapped
             avg_freqs, band_power, _, _ = ctx.speed_spectrum(freqs, fmask, positions=selected)
-        finally:
-            ctx.close()
         return self._over_atoms(avg_freqs, band_power, return_stdev)
 
     def compute_for_analysis(self, la, mask=None, return_stdev=False):
@@ -858,11 +855,8 @@ class MeanSquaredDisplacement(object):
         selected = _selected_columns(traj, mask)
         if selected.shape[1] == 0:
             return self._empty(len(selected), images)
-        ctx = _lib.HipContext(np.asarray(cell, dtype=np.float64) if self.unwrap else np.eye(3))
-        try:
+        with _lib.HipContext(np.asarray(cell, dtype=np.float64) if self.unwrap else np.eye(3)) as ctx:
             raw = self._call(ctx, images, positions=selected)
-        finally:
-            ctx.close()
         return self._result(len(selected), raw)
 
     def compute_for_analysis(self, la, mask=None, images=False):

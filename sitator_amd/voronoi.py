@@ -45,11 +45,8 @@ class VoronoiSiteGenerator(object):
         static = sn.static_structure
         positions = np.ascontiguousarray(static.get_positions(), dtype=np.float64)
         cell = np.asarray(static.cell, dtype=np.float64).reshape(3, 3)
-        ctx = _lib.HipContext(cell, device=self._device)
-        try:
+        with _lib.HipContext(cell, device=self._device) as ctx:
             res = ctx.voronoi_nodes(positions, self._tolerance)
-        finally:
-            ctx.close()
         self.last_info = res["info"]
         bad = np.nonzero(res["status"] != 0)[0]
         if len(bad):
