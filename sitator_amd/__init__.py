@@ -16,6 +16,7 @@ from .landmark import LandmarkAnalysis  # noqa: F401
 from .dynamics import (AverageVibrationalFrequency, GenerateClampedTrajectory, JumpAnalysis, MergeSitesByDynamics,  # noqa: F401
                        MergeSitesByThreshold, RemoveUnoccupiedSites, ReplaceUnassignedPositions, SmoothSiteTrajectory)
 from .dynamics import MeanSquaredDisplacement, MSDResult, diffusion_coefficient  # noqa: F401
+from .dynamics import VanHoveCorrelation, VanHoveResult, RadialDistribution, RDFResult  # noqa: F401
 from .merging import MergeSites, MergeSitesError, MergedSitesTooDistantError  # noqa: F401
 from .recenter import RecenterTrajectory  # noqa: F401
 from .misc import GenerateAroundSites, NAvgsPerSite  # noqa: F401

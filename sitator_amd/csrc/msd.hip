@@ -20,8 +20,7 @@
 #include "series.h"
 #include "spectrum_pass.h"
 #include "msd_plan.h"
-
-struct MsdCell { double cm[9], ci[9]; };
+#include "msd_series.h"
 
 // shift[c][a][t] = -image of the step t-1 -> t of atom c along cell vector a (0 at t = 0), through the tile of series.h
 // (the scans read a series as one run), and behind it the largest residual of the steps the workgroup looked at.
@@ -199,6 +198,21 @@ template <class Op> static int msd_scan(sit_ctx *c, Op op, i64 n_chunks, i64 n_s
     return SIT_OK;
 }
 
+int msd_series_launch(sit_ctx *c, const SeriesSource &src, i64 a0, i64 nb, i64 F, const MsdCell &cell, bool unwrap, i64 n_chunks,
+                      i32 *images, void *totals, double *y, u64 *status)
+{
+    const dim3 tiles((unsigned)((F + 31) / 32), (unsigned)((nb + 31) / 32));
+    if (unwrap) {
+        k_msd_shift<<<tiles, dim3(256), 0, c->stream>>>(src, a0, nb, F, cell, images, status);
+        HIP_TRY(c, hipGetLastError());
+        ScanImages si; si.v = images; si.F = F;
+        if (const int rc = msd_scan(c, si, n_chunks, 3 * nb, (i32 *)totals)) return rc;
+    }
+    k_msd_series<<<tiles, dim3(256), 0, c->stream>>>(src, a0, nb, F, cell, unwrap ? images : nullptr, y);
+    HIP_TRY(c, hipGetLastError());
+    return SIT_OK;
+}
+
 // msd of n_series series y [n_series][F] at the lags 0 .. n_lags - 1 into d_out [n_series][n_lags]
 static int msd_all_lags(sit_ctx *c, const MsdPlan &pl, const double2 *root, const double *d_y, double *d_psum, double *d_totals,
                         double2 *d_buf, double *d_out, i64 F, i64 n_lags, i64 n_series)
@@ -277,15 +291,7 @@ extern "C" int sit_msd(sit_ctx *c, const double *positions, i64 F, const i64 *at
     std::vector<i32> img_host(images ? (size_t)(3 * B * F) : 0);
     for (i64 a0 = 0; a0 < n_sel; a0 += B) {
         const i64 nb = a0 + B < n_sel ? B : n_sel - a0, n_series = 3 * nb;
-        const dim3 tiles((unsigned)((F + 31) / 32), (unsigned)((nb + 31) / 32));
-        if (unwrap) {
-            k_msd_shift<<<tiles, dim3(256), 0, c->stream>>>(src, a0, nb, F, cell, w.images, w.status);
-            HIP_TRY(c, hipGetLastError());
-            ScanImages si; si.v = w.images; si.F = F;
-            if ((rc = msd_scan(c, si, pl.n_chunks, n_series, (i32 *)w.totals))) return rc;
-        }
-        k_msd_series<<<tiles, dim3(256), 0, c->stream>>>(src, a0, nb, F, cell, unwrap ? w.images : nullptr, w.y);
-        HIP_TRY(c, hipGetLastError());
+        if ((rc = msd_series_launch(c, src, a0, nb, F, cell, unwrap != 0, pl.n_chunks, w.images, w.totals, w.y, w.status))) return rc;
         if (collective) {
             k_msd_collective<<<dim3((unsigned)((F + 255) / 256), 3), dim3(256), 0, c->stream>>>(w.y, nb, F, a0 == 0 ? 1 : 0, w.coll_y);
             HIP_TRY(c, hipGetLastError());

@@ -19,6 +19,9 @@ device-resident site assignments:
 * ``MeanSquaredDisplacement`` and ``diffusion_coefficient``  (no counterpart in the reference; the tracer and the collective
   mean squared displacement against the lag, unwrapped under the cell on the device, also straight from the trajectory a
   ``LandmarkAnalysis`` left resident)
+* ``VanHoveCorrelation`` and ``RadialDistribution``  (no counterpart in the reference; the self and the distinct part of the
+  van Hove function and ``g(r)`` as integer histograms of float64 minimum-image distances, also straight from the trajectory a
+  ``LandmarkAnalysis`` left resident)
 """
 import contextlib
 import logging
@@ -873,3 +876,136 @@ class MeanSquaredDisplacement(object):
         if len(atoms) == 0:
             return self._empty(ctx.F, images)
         return self._result(ctx.F, self._call(ctx, images, atoms=atoms))
+
+
+class VanHoveResult(object):
+    """What ``VanHoveCorrelation`` returns.
+
+    ``lags`` int64 ``[n_lags]`` (frames); ``edges`` ``[n_bins + 1]`` and ``r`` ``[n_bins]``, the bin edges and centres;
+    ``n_origins`` int64 ``[n_lags]``, the time origins of every lag; ``self_counts`` / ``distinct_counts`` uint64
+    ``[n_lags, n_bins + 1]`` as the device counted them, the last entry of a row being the overflow (everything at ``r_max``
+    or beyond, or not finite); ``self_density`` ``[n_lags, n_bins]`` = counts / (origins * n_a * dr), the probability density of
+    the displacement length ``4 pi r^2 G_s(r, tau)``, which integrates to one minus the overflow share; ``distinct``
+    ``[n_lags, n_bins]`` = counts * V / (origins * pairs * volume of the shell) = ``G_d(r, tau) / rho``, which is ``g(r)`` at lag
+    0.  A part that was not asked for is ``None``.  ``max_residual``: as ``MSDResult.max_residual`` (0 without unwrapping)."""
+
+    def __init__(self, lags, edges, n_origins, n_a, n_pairs, volume, self_counts, distinct_counts, max_residual):
+        self.lags, self.edges, self.n_origins = lags, edges, n_origins
+        self.r = 0.5 * (edges[:-1] + edges[1:])
+        self.self_counts, self.distinct_counts, self.max_residual = self_counts, distinct_counts, max_residual
+        self.n_a, self.n_pairs = n_a, n_pairs
+        n_bins = len(edges) - 1
+        dr = edges[-1] / n_bins
+        shells = (4.0 * np.pi / 3.0) * (edges[1:] ** 3 - edges[:-1] ** 3)
+        origins = n_origins.astype(np.float64)[:, None]
+        self.self_density = self.distinct = None
+        with np.errstate(divide="ignore", invalid="ignore"):
+            if self_counts is not None:
+                self.self_density = self_counts[:, :n_bins] / (origins * n_a * dr)
+            if distinct_counts is not None:
+                self.distinct = distinct_counts[:, :n_bins] * volume / (origins * n_pairs * shells[None, :])
+
+
+def _vanhove_edges(r_max, n_bins):
+    edges = np.arange(n_bins + 1, dtype=np.float64) * (float(r_max) / n_bins)
+    edges[-1] = float(r_max)
+    return edges
+
+
+class VanHoveCorrelation(object):
+    """The van Hove correlation function of chosen atoms against the lag time, as histograms of distances: the self part
+    ``G_s(r, tau)``, the distribution of ``|x_i(t + tau) - x_i(t)|`` (its peaks at the site-to-site distances show hopping), and
+    the distinct part ``G_d(r, tau)``, the distribution of ``|x_j(t + tau) - x_i(t)|`` over the pairs ``i != j`` of two
+    selections (at small ``r``: does an ion move into the place another one left).  The reference has no such operator; the
+    definitions are in ``DESIGN.md`` section 21.
+
+    ``lags``: the lags, in frames, each in ``[0, n_frames - 1]``.  ``r_max``, ``n_bins``: bins of equal width on
+    ``[0, r_max)``; ``r_max`` is at most half the smallest perpendicular height of the cell (less one part in 2^30), where
+    the rounded fractional difference is the true minimum image for any cell shape.  ``origin_stride``: every how many frames
+    a time origin is taken.  ``unwrap``: the self part follows the trajectory unwrapped under the cell as
+    ``MeanSquaredDisplacement`` does (``max_residual`` above 0.25 logs its warning); the distinct part reads the frames as
+    they are.  The counts come from HIP kernels (``sit_vanhove``) as integers added with integer atomics - the same bytes on
+    every call - and are normalised on the host in float64."""
+
+    def __init__(self, lags, r_max, n_bins, origin_stride=1, self_part=True, distinct_part=True, unwrap=True):
+        self.lags = np.array(lags, dtype=np.int64).reshape(-1)
+        self.r_max, self.n_bins, self.origin_stride = float(r_max), int(n_bins), int(origin_stride)
+        self.self_part, self.distinct_part, self.unwrap = bool(self_part), bool(distinct_part), bool(unwrap)
+        if not (self.self_part or self.distinct_part):
+            raise ValueError("Neither the self part nor the distinct part is asked for")
+        if self.n_bins < 1 or self.origin_stride < 1 or len(self.lags) < 1:
+            raise ValueError("n_bins, origin_stride and the number of lags must be at least 1")
+
+    def _run(self, ctx, a, b, same, n_frames, positions=None):
+        from . import _lib_vanhove
+        if len(a) == 0 or len(b) == 0:
+            raise ValueError("A selection holds no atom")
+        sc, dc, res = _lib_vanhove.vanhove(ctx, a, b, self.lags, self.r_max, self.n_bins, positions=positions, same=same,
+                                           origin_stride=self.origin_stride, unwrap=self.unwrap, self_part=self.self_part,
+                                           distinct_part=self.distinct_part)
+        if self.unwrap and self.self_part and res > 0.25:
+            logger.warning("VanHoveCorrelation: a step of %.3f cell vectors from the nearest whole number of them - a "
+                           "step of a quarter of the cell is not molecular dynamics; the unwrapping may be wrong." % res)
+        n_origins = (n_frames - 1 - self.lags) // self.origin_stride + 1
+        n_pairs = len(a) * len(b) - (len(a) if same else 0)
+        return VanHoveResult(self.lags, _vanhove_edges(self.r_max, self.n_bins), n_origins, len(a), n_pairs,
+                             abs(float(np.linalg.det(ctx.cell))), sc, dc, res)
+
+    def compute(self, traj, cell, mask, mask_b=None):
+        """``traj``: a host trajectory ``[n_frames, n_atoms, 3]``, float64, not modified; ``cell``: rows are the cell vectors;
+        ``mask`` / ``mask_b``: the two selections, boolean masks or index arrays (whatever ``traj[:, mask]`` takes);
+        ``mask_b=None``: the same selection, pairs of an atom with itself left out.  Returns a ``VanHoveResult``.
+        ``ValueError`` for another dtype, an empty selection, a lag beyond ``n_frames - 1``, ``r_max`` beyond half the
+        smallest height of the cell or a degenerate cell."""
+        sel = _selected_columns(traj, mask)
+        n_a = sel.shape[1]
+        a = b = np.arange(n_a, dtype=np.int64)
+        if mask_b is not None:
+            sel_b = _selected_columns(traj, mask_b)
+            b = n_a + np.arange(sel_b.shape[1], dtype=np.int64)
+            sel = np.ascontiguousarray(np.concatenate([sel, sel_b], axis=1))
+        with _lib.HipContext(np.asarray(cell, dtype=np.float64)) as ctx:
+            return self._run(ctx, a, b, mask_b is None, len(sel), positions=sel)
+
+    def compute_for_analysis(self, la, mask=None, mask_b=None):
+        """The same from the trajectory a ``LandmarkAnalysis`` that has run left on its GPU, under that analysis' cell: no
+        upload.  ``mask``: boolean mask or index array over the atoms of a frame, ``None``: the mobile atoms of the run;
+        ``mask_b=None``: the same selection.  Frames the analysis recentred on the device are accepted, as
+        ``MeanSquaredDisplacement.compute_for_analysis`` accepts them; ``NotImplementedError`` after a run over frame shards."""
+        ctx, a = _resident_columns(la, mask, "VanHoveCorrelation")
+        b = a if mask_b is None else _resident_columns(la, mask_b, "VanHoveCorrelation")[1]
+        return self._run(ctx, a, b, mask_b is None, ctx.F)
+
+
+class RDFResult(object):
+    """What ``RadialDistribution`` returns: ``r`` ``[n_bins]`` and ``edges`` ``[n_bins + 1]``; ``g`` ``[n_bins]``, the radial
+    distribution function of the ``b`` atoms around the ``a`` atoms; ``counts`` uint64 ``[n_bins + 1]`` as the device counted
+    them over all frames taken (the last entry: pairs at ``r_max`` or beyond); ``n`` ``[n_bins]``, the running coordination
+    number ``cumsum(counts) / (frames taken * n_a)`` at the upper edge of every bin; ``n_origins``, the frames taken."""
+
+    def __init__(self, vh):
+        self.r, self.edges = vh.r, vh.edges
+        self.g, self.counts, self.n_origins = vh.distinct[0], vh.distinct_counts[0], int(vh.n_origins[0])
+        self.n = np.cumsum(self.counts[:-1]) / (float(self.n_origins) * vh.n_a)
+
+
+class RadialDistribution(object):
+    """The radial distribution function ``g(r)`` between two selections of atoms, averaged over every ``frame_stride``-th
+    frame: the distinct part of ``VanHoveCorrelation`` at lag 0 alone, by the same kernels; ``r_max`` and ``n_bins`` as there."""
+
+    def __init__(self, r_max, n_bins, frame_stride=1):
+        self._vh = VanHoveCorrelation([0], r_max, n_bins, origin_stride=frame_stride, self_part=False, unwrap=False)
+
+    def compute(self, traj, cell, mask_a, mask_b=None):
+        """``mask_b=None``: among the atoms of ``mask_a``.  Returns an ``RDFResult``; the errors of ``VanHoveCorrelation.compute``."""
+        return RDFResult(self._vh.compute(traj, cell, mask_a, mask_b))
+
+    def compute_for_analysis(self, la, mask_a=None, mask_b="static"):
+        """From the frames an analysis left resident.  ``mask_a=None``: the mobile atoms; ``mask_b``: ``"static"`` for the static
+        atoms of the run, ``None`` for the atoms of ``mask_a``, else a mask or an index array."""
+        if isinstance(mask_b, str):
+            if mask_b != "static":
+                raise ValueError("mask_b is a mask, an index array, None or \"static\"")
+            _resident_columns(la, mask_a, "RadialDistribution")      # has run, on one GPU
+            mask_b = np.asarray(la._static_idx, dtype=np.int64)
+        return RDFResult(self._vh.compute_for_analysis(la, mask_a, mask_b))

@@ -179,6 +179,7 @@ class LandmarkAnalysis(object):
         static_idx = np.where(sn.static_mask)[0]
         mobile_idx = np.where(sn.mobile_mask)[0]
         self._mobile_idx = mobile_idx          # the mobile columns of the resident frames (AverageVibrationalFrequency)
+        self._static_idx = static_idx          # the static ones (RadialDistribution)
         prefit = None
         self._pipelined = False
         if hasattr(ctx, "prefault_assignments") and os.environ.get("SITATOR_PREFAULT", "1") != "0":
