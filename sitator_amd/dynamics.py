@@ -1009,3 +1009,166 @@ class RadialDistribution(object):
             _resident_columns(la, mask_a, "RadialDistribution")      # has run, on one GPU
             mask_b = np.asarray(la._static_idx, dtype=np.int64)
         return RDFResult(self._vh.compute_for_analysis(la, mask_a, mask_b))
+
+
+def q_vectors(cell, q_max, half_space=True):
+    """The integer triples ``(h, k, l)`` int64 ``[n_q, 3]`` of the q vectors ``q = 2 pi (h ci[0] + k ci[1] + l ci[2])``
+    (``ci = inverse(cell^T)``: the reciprocal lattice of the cell, the only q vectors a periodic trajectory defines without
+    unwrapping) with ``0 < |q| <= q_max``, ordered by ``|q|`` and then by index.  ``half_space``: one of every pair ``+-q`` - the
+    one whose first non-zero index is positive - since ``F(-q, tau) = conj F(q, tau)``.  ``ValueError`` for a ``q_max`` that needs
+    an index beyond 32, with the number of cell lengths it asks for."""
+    cell = np.asarray(cell, dtype=np.float64)
+    q_max = float(q_max)
+    if cell.shape != (3, 3) or not q_max > 0.0 or not np.isfinite(q_max):
+        raise ValueError("q_vectors needs a 3 x 3 cell and a finite q_max above 0")
+    recip = 2.0 * np.pi * np.linalg.inv(cell.T)                       # rows: 2 pi ci[a]
+    # |index a| <= q_max |c_a| / (2 pi): q . c_a = 2 pi (index a) and |q . c_a| <= |q| |c_a|
+    need = np.floor(q_max * np.linalg.norm(cell, axis=1) / (2.0 * np.pi) * (1.0 + 1e-12)).astype(np.int64)
+    if np.any(need > 32):
+        raise ValueError("q_max = %g needs an index of %d along a cell vector: a wavelength of 1/%d of that cell length, beyond "
+                         "the 32 the device tables hold" % (q_max, need.max(), need.max()))
+    grids = np.meshgrid(*[np.arange(-n, n + 1) for n in need], indexing="ij")
+    hkl = np.stack([g.reshape(-1) for g in grids], axis=1).astype(np.int64)
+    norm = np.linalg.norm(hkl.astype(np.float64) @ recip, axis=1)
+    keep = (norm <= q_max) & np.any(hkl != 0, axis=1)
+    if half_space:
+        first = hkl[np.arange(len(hkl)), np.argmax(hkl != 0, axis=1)]
+        keep &= first > 0
+    hkl, norm = hkl[keep], norm[keep]
+    order = np.lexsort((hkl[:, 2], hkl[:, 1], hkl[:, 0], norm))
+    return np.ascontiguousarray(hkl[order])
+
+
+def _shell_average(q_norm, values, edges):
+    """``(mean [..., n_bins], count [n_bins])`` of ``values [..., n_q]`` over the q vectors of every bin ``edges[k] <= |q| <
+    edges[k + 1]``; NaN where a bin holds none."""
+    edges = np.asarray(edges, dtype=np.float64).reshape(-1)
+    which = np.searchsorted(edges, q_norm, "right") - 1
+    n_bins = len(edges) - 1
+    inside = (which >= 0) & (which < n_bins)
+    count = np.bincount(which[inside], minlength=n_bins)
+    values = np.asarray(values)
+    out = np.full(values.shape[:-1] + (n_bins,), np.nan, dtype=values.dtype)
+    for k in np.nonzero(count)[0]:
+        out[..., k] = values[..., inside & (which == k)].mean(axis=-1)
+    return out, count
+
+
+class ScatteringResult(object):
+    """What ``IntermediateScattering`` returns.
+
+    ``q_int`` int64 ``[n_q, 3]``, ``q`` ``[n_q, 3]`` the Cartesian vectors and ``q_norm`` ``[n_q]``; ``lags`` int64 ``[n_lags]``
+    and ``n_origins`` int64 ``[n_lags]``; ``self_sums`` / ``coherent_sums`` complex128 ``[n_lags, n_q]`` as the device summed
+    them; ``self`` = sums / (origins n_a), ``coherent`` = sums / (origins sqrt(n_a n_b)) and, for one selection, ``distinct`` =
+    coherent - self.  A part that was not asked for, or is not defined, is ``None``."""
+
+    def __init__(self, q_int, cell, lags, n_origins, n_a, n_b, same, self_sums, coherent_sums):
+        self.q_int, self.lags, self.n_origins = q_int, lags, n_origins
+        self.q = q_int.astype(np.float64) @ (2.0 * np.pi * np.linalg.inv(np.asarray(cell, dtype=np.float64).T))
+        self.q_norm = np.linalg.norm(self.q, axis=1)
+        self.n_a, self.n_b = n_a, n_b
+        self.self_sums, self.coherent_sums = self_sums, coherent_sums
+        origins = n_origins.astype(np.float64)[:, None]
+        self.self = None if self_sums is None else self_sums / (origins * n_a)
+        self.coherent = None if coherent_sums is None else coherent_sums / (origins * np.sqrt(float(n_a) * float(n_b)))
+        self.distinct = self.coherent - self.self if (same and self.self is not None and self.coherent is not None) else None
+
+    def shell_average(self, edges):
+        """``(self, coherent, distinct, count)``: the mean of each part ``[n_lags, n_bins]`` over the q vectors whose ``|q|`` lies
+        in every bin of ``edges`` (``None`` for a part that is), and the q vectors per bin; NaN where a bin holds none."""
+        parts = [None if v is None else _shell_average(self.q_norm, v, edges)[0] for v in (self.self, self.coherent, self.distinct)]
+        return parts[0], parts[1], parts[2], _shell_average(self.q_norm, np.zeros(len(self.q_norm)), edges)[1]
+
+
+class IntermediateScattering(object):
+    """The intermediate scattering function of chosen atoms over q vectors commensurate with the cell: the self part
+    ``F_s(q, tau)`` = mean over atoms and origins of ``exp(i q . (x_i(t + tau) - x_i(t)))`` (what quasi-elastic neutron scattering
+    measures; its decay against ``|q|`` confronts a hopping model with the trajectory) and the coherent part ``F(q, tau)`` =
+    ``<rho_b(q, t + tau) conj rho_a(q, t)> / sqrt(n_a n_b)`` with ``rho(q, t) = sum_i exp(i q . x_i(t))``, whose lag-0 value is
+    the static structure factor.  The reference has no such operator; the definitions are in ``DESIGN.md`` section 22.
+
+    ``q_int``: integer triples ``[n_q, 3]``, each index within +-32 (``q_vectors`` makes them); ``lags``: the lags, in frames,
+    each in ``[0, n_frames - 1]``; ``origin_stride``: every how many frames a time origin is taken.  For these q vectors the
+    phase of an atom does not change when it moves by a cell vector, so the trajectory is read as it is, wrapped or not.  The
+    sums come from HIP kernels (``sit_scattering``) in float64 with a sine and cosine of the library's own and a fixed order - the
+    same bytes on every call - and are normalised on the host."""
+
+    def __init__(self, q_int, lags, origin_stride=1, self_part=True, coherent_part=True):
+        self.q_int = np.ascontiguousarray(np.array(q_int, dtype=np.int64).reshape(-1, 3))
+        self.lags = np.array(lags, dtype=np.int64).reshape(-1)
+        self.origin_stride = int(origin_stride)
+        self.self_part, self.coherent_part = bool(self_part), bool(coherent_part)
+        if not (self.self_part or self.coherent_part):
+            raise ValueError("Neither the self part nor the coherent part is asked for")
+        if len(self.q_int) < 1 or self.origin_stride < 1 or len(self.lags) < 1:
+            raise ValueError("The number of q vectors, origin_stride and the number of lags must be at least 1")
+
+    def _run(self, ctx, a, b, same, n_frames, positions=None):
+        from . import _lib_scattering
+        if len(a) == 0 or len(b) == 0:
+            raise ValueError("A selection holds no atom")
+        if self.self_part and not same:
+            raise ValueError("The self part is that of one selection: leave mask_b out, or ask for self_part=False")
+        ss, cs = _lib_scattering.scattering(ctx, a, b, self.q_int, self.lags, positions=positions, same=same,
+                                            origin_stride=self.origin_stride, self_part=self.self_part, coherent_part=self.coherent_part)
+        n_origins = (n_frames - 1 - self.lags) // self.origin_stride + 1
+        return ScatteringResult(self.q_int, ctx.cell, self.lags, n_origins, len(a), len(b), same, ss, cs)
+
+    def compute(self, traj, cell, mask, mask_b=None):
+        """``traj``: a host trajectory ``[n_frames, n_atoms, 3]``, float64, not modified; ``cell``: rows are the cell vectors;
+        ``mask`` / ``mask_b``: the selections, boolean masks or index arrays (whatever ``traj[:, mask]`` takes); ``mask_b=None``:
+        one selection.  Returns a ``ScatteringResult``.  ``ValueError`` for another dtype, an empty selection, a lag beyond
+        ``n_frames - 1``, an index beyond 32, a degenerate cell, or the self part with ``mask_b`` given."""
+        sel = _selected_columns(traj, mask)
+        n_a = sel.shape[1]
+        a = b = np.arange(n_a, dtype=np.int64)
+        if mask_b is not None:
+            sel_b = _selected_columns(traj, mask_b)
+            b = n_a + np.arange(sel_b.shape[1], dtype=np.int64)
+            sel = np.ascontiguousarray(np.concatenate([sel, sel_b], axis=1))
+        with _lib.HipContext(np.asarray(cell, dtype=np.float64)) as ctx:
+            return self._run(ctx, a, b, mask_b is None, len(sel), positions=sel)
+
+    def compute_for_analysis(self, la, mask=None, mask_b=None):
+        """The same from the trajectory a ``LandmarkAnalysis`` that has run left on its GPU, under that analysis' cell: no
+        upload.  ``mask``: boolean mask or index array over the atoms of a frame, ``None``: the mobile atoms of the run;
+        ``mask_b=None``: the same selection.  ``NotImplementedError`` after a run over frame shards."""
+        ctx, a = _resident_columns(la, mask, "IntermediateScattering")
+        b = a if mask_b is None else _resident_columns(la, mask_b, "IntermediateScattering")[1]
+        return self._run(ctx, a, b, mask_b is None, ctx.F)
+
+
+class StructureFactorResult(object):
+    """What ``StructureFactor`` returns: ``q_int``, ``q``, ``q_norm`` as ``ScatteringResult``; ``S`` ``[n_q]``, real for one
+    selection (``<|rho(q)|^2> / n``) and complex for a partial between two; ``sums`` complex128 ``[n_q]`` as the device summed
+    them; ``n_origins``, the frames taken; ``shell_average(edges)`` -> ``(mean of S per |q| bin, q vectors per bin)``."""
+
+    def __init__(self, res, same):
+        self.q_int, self.q, self.q_norm = res.q_int, res.q, res.q_norm
+        self.sums, self.n_origins = res.coherent_sums[0], int(res.n_origins[0])
+        self.S = res.coherent[0].real.copy() if same else res.coherent[0]
+
+    def shell_average(self, edges):
+        return _shell_average(self.q_norm, self.S, edges)
+
+
+class StructureFactor(object):
+    """The static structure factor ``S(q)`` of a selection, or the partial one between two, averaged over every
+    ``frame_stride``-th frame: the coherent part of ``IntermediateScattering`` at lag 0 alone, by the same kernels."""
+
+    def __init__(self, q_int, frame_stride=1):
+        self._isf = IntermediateScattering(q_int, [0], origin_stride=frame_stride, self_part=False)
+
+    def compute(self, traj, cell, mask_a, mask_b=None):
+        """``mask_b=None``: the atoms of ``mask_a`` among themselves.  The errors of ``IntermediateScattering.compute``."""
+        return StructureFactorResult(self._isf.compute(traj, cell, mask_a, mask_b), mask_b is None)
+
+    def compute_for_analysis(self, la, mask_a=None, mask_b=None):
+        """From the frames an analysis left resident.  ``mask_a=None``: the mobile atoms; ``mask_b``: ``None`` for the atoms of
+        ``mask_a``, ``"static"`` for the static atoms of the run, else a mask or an index array."""
+        if isinstance(mask_b, str):
+            if mask_b != "static":
+                raise ValueError("mask_b is a mask, an index array, None or \"static\"")
+            _resident_columns(la, mask_a, "StructureFactor")          # has run, on one GPU
+            mask_b = np.asarray(la._static_idx, dtype=np.int64)
+        return StructureFactorResult(self._isf.compute_for_analysis(la, mask_a, mask_b), mask_b is None)
