@@ -18,6 +18,7 @@ from .dynamics import (AverageVibrationalFrequency, GenerateClampedTrajectory, J
 from .dynamics import MeanSquaredDisplacement, MSDResult, diffusion_coefficient  # noqa: F401
 from .dynamics import VanHoveCorrelation, VanHoveResult, RadialDistribution, RDFResult  # noqa: F401
 from .dynamics import IntermediateScattering, ScatteringResult, StructureFactor, StructureFactorResult, q_vectors  # noqa: F401
+from .density import DensityResult, IonicDensity, gaussian_stencil  # noqa: F401
 from .merging import MergeSites, MergeSitesError, MergedSitesTooDistantError  # noqa: F401
 from .recenter import RecenterTrajectory  # noqa: F401
 from .misc import GenerateAroundSites, NAvgsPerSite  # noqa: F401
