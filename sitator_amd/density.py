@@ -51,6 +51,18 @@ def gaussian_stencil(cell, grid, sigma, cutoff=4.0):
     return taps, w / w.sum()
 
 
+def voxel_of(cell, grid, points):
+    """The voxel (flat index) of Cartesian points on the grid ``(n0, n1, n2)`` over ``cell``, by the rule of the kernels."""
+    ci = np.linalg.inv(np.asarray(cell, dtype=np.float64).T)
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    idx = []
+    for a in range(3):
+        s = (ci[a, 0] * p[:, 0] + ci[a, 1] * p[:, 1]) + ci[a, 2] * p[:, 2]
+        i = ((s - np.floor(s)) * float(grid[a])).astype(np.int64)
+        idx.append(np.where(i >= grid[a], grid[a] - 1, i))
+    return (idx[0] * grid[1] + idx[1]) * grid[2] + idx[2]
+
+
 class DensityResult(object):
     """What ``IonicDensity`` returns.  ``counts`` uint64 ``[n_classes, n0, n1, n2]`` as the device counted them; ``n_frames``, the
     frames taken; ``skipped``, the entries with a coordinate that is not finite; ``voxel_volume`` in A^3; ``density`` =
@@ -111,16 +123,20 @@ class DensityResult(object):
         fr = self.fractional_centers().reshape(-1, 3)[v]
         return v, fr, fr @ self.cell, values
 
+    def components(self, level, connectivity=26, plane=None, ctx=None):
+        """The connected components of ``{g >= level}`` of the smoothed grid if there is one, else the raw one, with the rank and the
+        basis of every component's loop lattice: a ``ComponentsResult`` (``percolation.py``)."""
+        from .percolation import density_components
+        return density_components(self._plane(plane), self.cell, level, connectivity, ctx=ctx)
+
+    def percolation(self, connectivity=26, plane=None, ctx=None):
+        """The levels at which that grid first connects across the cell in one, two and three dimensions: a ``PercolationResult``."""
+        from .percolation import density_percolation
+        return density_percolation(self._plane(plane), self.cell, connectivity, ctx=ctx)
+
     def voxel_of(self, points):
         """The voxel (flat index) of Cartesian points, by the rule of the kernels."""
-        ci = np.linalg.inv(self.cell.T)
-        p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
-        idx = []
-        for a in range(3):
-            s = (ci[a, 0] * p[:, 0] + ci[a, 1] * p[:, 1]) + ci[a, 2] * p[:, 2]
-            i = ((s - np.floor(s)) * float(self.grid[a])).astype(np.int64)
-            idx.append(np.where(i >= self.grid[a], self.grid[a] - 1, i))
-        return (idx[0] * self.grid[1] + idx[1]) * self.grid[2] + idx[2]
+        return voxel_of(self.cell, self.grid, points)
 
     def match_sites(self, sn, min_fraction=0.05, plane=None):
         """How the density and the sites of ``sn`` agree: a dict with ``site_density`` (the density at the voxel of every site
