@@ -224,6 +224,33 @@ def load():
     return _lib
 
 
+def bind_signatures(lib, flag, signatures):
+    """Sets ``argtypes`` / ``restype`` of every symbol of a further header's table on ``lib`` (once: ``flag`` is the attribute
+    that remembers it) and returns ``lib``."""
+    if not getattr(lib, flag, False):
+        for name, (res, args) in signatures.items():
+            fn = getattr(lib, name)
+            fn.restype = res
+            fn.argtypes = args
+        setattr(lib, flag, True)
+    return lib
+
+
+def _triple(v, what):
+    v = _i64(v).reshape(-1)
+    if len(v) != 3:
+        raise ValueError("%s holds one number per axis" % what)
+    return v
+
+
+def _grid3(grid):
+    """``(grid as float64, its shape as int64)`` of a 3-D array."""
+    grid = _f64(grid)
+    if grid.ndim != 3:
+        raise ValueError("grid is a 3-D array")
+    return grid, _i64(grid.shape)
+
+
 def comm_unique_id():
     """ncclGetUniqueId: 128 bytes that rank 0 makes and every rank of the job receives."""
     uid = np.zeros(128, dtype=np.uint8)

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import _d, _i, _i32, _i64, _f64, _ptr, _dp, _ip, _i32p, _u64p, _vp, i64
+from ._lib import _d, _i, _i32, _i64, _f64, _grid3, _ptr, _triple, _dp, _ip, _i32p, _u64p, _vp, i64
 
 # every symbol include/sitator_hip_density.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -21,20 +21,7 @@ PLAN_KEYS = ["threads", "table_slots", "probe_limit", "lds_bytes", "frames_per_r
 
 def bind(lib):
     """Sets ``argtypes`` / ``restype`` of the three symbols on ``lib`` (once) and returns it."""
-    if not getattr(lib, "_density_bound", False):
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._density_bound = True
-    return lib
-
-
-def _triple(v, what):
-    v = _i64(v).reshape(-1)
-    if len(v) != 3:
-        raise ValueError("%s holds one number per axis" % what)
-    return v
+    return _lib.bind_signatures(lib, "_density_bound", SIGNATURES)
 
 
 def density_plan(F, A, n_sel, grid, frame_stride=1, K=0, n_classes=1, n_taps=0, halo=(0, 0, 0), form=0, host=True, workspace_bytes=0):
@@ -90,9 +77,6 @@ def density(ctx, atoms, grid, positions=None, frame_stride=1, site_class=None, n
 def density_peaks(ctx, grid, threshold):
     """The voxels (int64, ascending) of the 3-D float64 array ``grid`` that pass the peak rule of ``sit_density_peaks``."""
     lib = bind(ctx.lib)
-    grid = _f64(grid)
-    if grid.ndim != 3:
-        raise ValueError("grid is a 3-D array")
-    g = _i64(grid.shape)
+    grid, g = _grid3(grid)
     rec = ctx._records(1, lambda cap, out, n: lib.sit_density_peaks(ctx._h, _d(grid), _i(g), float(threshold), cap, out, n))
     return np.ascontiguousarray(rec[:, 0])

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import _d, _i, _f64, _i64, _ptr, _dp, _ip, _i32p, _vp, i64
+from ._lib import _d, _i, _grid3, _ptr, _triple, _dp, _ip, _i32p, _vp, i64
 
 # every symbol include/sitator_hip_percolation.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -22,20 +22,7 @@ RECORD_WORDS = 12                                                   # root, size
 
 def bind(lib):
     """Sets ``argtypes`` / ``restype`` of the three symbols on ``lib`` (once) and returns it."""
-    if not getattr(lib, "_percolation_bound", False):
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._percolation_bound = True
-    return lib
-
-
-def _grid(grid):
-    grid = _f64(grid)
-    if grid.ndim != 3:
-        raise ValueError("grid is a 3-D array")
-    return grid, _i64(grid.shape)
+    return _lib.bind_signatures(lib, "_percolation_bound", SIGNATURES)
 
 
 def percolation_plan(grid, connectivity=26, form=0):
@@ -43,9 +30,7 @@ def percolation_plan(grid, connectivity=26, form=0):
     its LDS bytes, the form that 0 resolves to, the seam records of the full grid and the bytes of the work area.  Whatever the
     calls would refuse of these arguments: ``ValueError``."""
     lib = bind(_lib.load())
-    g = _i64(grid).reshape(-1)
-    if len(g) != 3:
-        raise ValueError("grid holds one number per axis")
+    g = _triple(grid, "grid")
     rc, plan = _lib._plan(PLAN_KEYS, lambda out: lib.sit_percolation_plan(_i(g), int(connectivity), int(form), out))
     if rc != _lib.OK:
         raise ValueError("percolation_plan: an axis outside [1, 1024], more than 2^27 voxels, a connectivity other than 6, 18, 26 or a "
@@ -58,7 +43,7 @@ def percolation_components(ctx, grid, level, connectivity=26, form=0, want_label
     (``None`` with ``want_labels=False``), ``records`` int64 ``[n, 12]`` - root, size, rank and the nine entries of the basis of
     every component in ascending root - and ``info`` = (rounds, seam records, form taken, distinct seam records)."""
     lib = bind(ctx.lib)
-    grid, g = _grid(grid)
+    grid, g = _grid3(grid)
     labels = np.empty(grid.shape, dtype=np.int32) if want_labels else None
     info = np.zeros(4, dtype=np.int64)
     rec = ctx._records(RECORD_WORDS, lambda cap, out, n: lib.sit_percolation_components(
@@ -70,7 +55,7 @@ def percolation_levels(ctx, grid, connectivity=26, form=0):
     """``(levels float64 [3], ranks int32 [3], info)`` of ``sit_percolation_levels``: ``info`` = (labelling passes, rounds of the
     last pass, seam records of the last pass, form taken)."""
     lib = bind(ctx.lib)
-    grid, g = _grid(grid)
+    grid, g = _grid3(grid)
     levels = np.zeros(3, dtype=np.float64)
     ranks = np.zeros(3, dtype=np.int32)
     info = np.zeros(4, dtype=np.int64)

@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import _d, _i, _i64, _ptr, _dp, _ip, _vp, i64
+from ._lib import _d, _i, _i64, _ptr, _triple, _dp, _ip, _vp, i64
 
 # every symbol include/sitator_hip_scattering.h declares: (restype, argtypes)
 SIGNATURES = {
@@ -20,13 +20,7 @@ PLAN_KEYS = ["threads", "max_index", "origins_per_block", "tile_entries", "lds_b
 
 def bind(lib):
     """Sets ``argtypes`` / ``restype`` of the two symbols on ``lib`` (once) and returns it."""
-    if not getattr(lib, "_scattering_bound", False):
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._scattering_bound = True
-    return lib
+    return _lib.bind_signatures(lib, "_scattering_bound", SIGNATURES)
 
 
 def _q_list(q_int):
@@ -42,9 +36,7 @@ def scattering_plan(F, n_a, n_b, n_q, h_max, n_lags, origin_stride=1, same=False
     lags per launch a workspace cap allows.  ``h_max``: the largest ``|index|`` of every axis of the q list.  Whatever
     ``scattering`` would refuse of these arguments: ``ValueError``."""
     lib = bind(_lib.load())
-    H = _i64(h_max).reshape(-1)
-    if len(H) != 3:
-        raise ValueError("h_max holds one number per axis")
+    H = _triple(h_max, "h_max")
     rc, plan = _lib._plan(PLAN_KEYS, lambda out: lib.sit_scattering_plan(int(F), int(n_a), int(n_b), int(bool(same)), int(n_q), _i(H), int(n_lags),
                                                                           int(origin_stride), int(bool(self_part)), int(bool(coherent_part)),
                                                                           int(workspace_bytes), out))

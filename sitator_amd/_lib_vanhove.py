@@ -21,13 +21,7 @@ PLAN_KEYS = ["threads", "max_bins", "max_atoms", "origins_per_workgroup", "b_spa
 
 def bind(lib):
     """Sets ``argtypes`` / ``restype`` of the two symbols on ``lib`` (once) and returns it."""
-    if not getattr(lib, "_vanhove_bound", False):
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(lib, name)
-            fn.restype = res
-            fn.argtypes = args
-        lib._vanhove_bound = True
-    return lib
+    return _lib.bind_signatures(lib, "_vanhove_bound", SIGNATURES)
 
 
 def vanhove_plan(F, n_a, n_b, n_lags, n_bins, origin_stride=1, self_part=True, distinct_part=True, unwrap=True, workspace_bytes=0):

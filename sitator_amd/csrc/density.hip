@@ -18,7 +18,6 @@
 #include <vector>
 
 #include "series.h"
-#include "msd_series.h"
 #include "density_plan.h"
 #include "sitator_hip_density.h"
 
@@ -250,16 +249,13 @@ extern "C" int sit_density(sit_ctx *c, const double *positions, i64 F, i64 A, co
     const DnPlan pl = dn_plan(in, sp_knobs_from_env().workspace);
     if (pl.err) { c->msg = std::string("sit_density: ") + pl.err; return SIT_ERR_INVALID; }
     for (i64 k = 0; k < n_taps; k++) SIT_REQUIRE(c, std::isfinite(weights[k]), "sit_density: a weight is not finite");
+    int rc;
     MsdCell cell;
-    for (int i = 0; i < 9; i++) { cell.cm[i] = c->pbc.cm[i]; cell.ci[i] = c->pbc.ci[i]; }
-    SIT_REQUIRE(c, dn_cell_ok(cell.cm, cell.ci), "sit_density: a degenerate cell");
-    if (!positions) {
-        SIT_REQUIRE(c, c->d_frames && c->A > 0, "sit_density: no resident frames (sit_set_frames first)");
-        SIT_REQUIRE(c, F == c->F && A == c->A, "sit_density: F or A is not that of the resident frames");
-    }
-    i64 bad = dn_first_outside(atoms, n_sel, 0, A - 1);
+    if ((rc = series_cell(c, "sit_density", &cell, "a degenerate cell"))) return rc;
+    if (!positions && (rc = series_resident(c, "sit_density", F, A))) return rc;
+    i64 bad = series_first_outside(atoms, n_sel, 0, A - 1);
     if (bad >= 0) return dn_refuse(c, "sit_density", "atom", atoms[bad], A);
-    if (site_class && (bad = dn_first_outside(site_class, K, 0, n_classes - 2)) >= 0)
+    if (site_class && (bad = series_first_outside(site_class, K, 0, n_classes - 2)) >= 0)
         return dn_refuse(c, "sit_density", "class", site_class[bad], n_classes - 1);
     HIP_TRY(c, hipSetDevice(c->device));
     if (site_class && !positions) {                               // the selection is the label columns, in order
@@ -270,7 +266,6 @@ extern "C" int sit_density(sit_ctx *c, const double *positions, i64 F, i64 A, co
         for (i64 i = 0; i < n_sel; i++)
             SIT_REQUIRE(c, atoms[i] == mobile[(size_t)i], "sit_density: the selection is not the label columns in order");
     }
-    int rc;
     Scoped work(c);
     DnPieces w;
     if ((rc = carve_scratch(c, [&](Carve &cv) { w = dn_layout(cv, pl, in); }, &work))) return rc;

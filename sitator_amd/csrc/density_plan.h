@@ -19,7 +19,7 @@
 #include <stdint.h>
 
 #include "scratch_carve.h"
-#include "msd_plan.h"
+#include "series_plan.h"
 
 #define DN_THREADS 256                            // threads of a workgroup of every kernel: four waves
 #define DN_MAX_GRID 1024                          // voxels along an axis
@@ -110,22 +110,9 @@ inline bool dn_halo(const int64_t *taps, int64_t n_taps, const int64_t *n, int64
     return true;
 }
 
-// the first element of list outside [lo, hi], or -1
-template <typename T> inline int64_t dn_first_outside(const T *list, int64_t n, int64_t lo, int64_t hi)
-{
-    for (int64_t i = 0; i < n; i++)
-        if (list[i] < lo || list[i] > hi) return i;
-    return -1;
-}
-
-// cm = cell^T and its inverse: a finite determinant other than 0 and a finite inverse
-inline bool dn_cell_ok(const double *m, const double *ci)
-{
-    const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-    bool ok = fabs(det) < INFINITY && det != 0.0;
-    for (int i = 0; i < 9; i++) ok = ok && fabs(ci[i]) < INFINITY;
-    return ok;
-}
+// the names the probe of tests/test_density_plan.py asks for; the library calls the shared ones of series_plan.h
+template <typename T> inline int64_t dn_first_outside(const T *list, int64_t n, int64_t lo, int64_t hi) { return series_first_outside(list, n, lo, hi); }
+inline bool dn_cell_ok(const double *m, const double *ci) { return series_cell_ok(m, ci); }
 
 // ---- the plan -----------------------------------------------------------------------------------------------------------
 struct DnPlanIn {

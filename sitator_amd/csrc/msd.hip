@@ -246,13 +246,7 @@ extern "C" int sit_msd(sit_ctx *c, const double *positions, i64 F, const i64 *at
     const bool direct = lags != nullptr;
     if (direct) {
         SIT_REQUIRE(c, n_lags >= 1, "sit_msd: an empty lag list");
-        for (i64 i = 0; i < n_lags; i++)
-            if (lags[i] < 0 || lags[i] > F - 1) {
-                char text[128];
-                snprintf(text, sizeof(text), "sit_msd: lag %lld is outside [0, %lld]", (long long)lags[i], (long long)(F - 1));
-                c->msg = text;
-                return SIT_ERR_INVALID;
-            }
+        if (const int rc = series_lags(c, "sit_msd", lags, n_lags, F)) return rc;
     } else {
         SIT_REQUIRE(c, max_lag >= 0 && max_lag <= F - 1, "sit_msd: max_lag is outside [0, F - 1]");
         SIT_REQUIRE(c, !r4, "sit_msd: the fourth moment comes with an explicit lag list only");
@@ -263,21 +257,14 @@ extern "C" int sit_msd(sit_ctx *c, const double *positions, i64 F, const i64 *at
     if (max_residual) *max_residual = 0.0;
     if (n_sel == 0) return SIT_OK;
     SIT_REQUIRE(c, msd, "sit_msd: missing array");
+    int rc;
     MsdCell cell;
-    for (int i = 0; i < 9; i++) { cell.cm[i] = c->pbc.cm[i]; cell.ci[i] = c->pbc.ci[i]; }
-    if (unwrap) {
-        const double *m = cell.cm;
-        const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-        bool ok = std::isfinite(det) && det != 0.0;
-        for (int i = 0; i < 9; i++) ok = ok && std::isfinite(cell.ci[i]);
-        SIT_REQUIRE(c, ok, "sit_msd: a degenerate cell cannot unwrap a trajectory");
-    }
+    if ((rc = series_cell(c, "sit_msd", &cell, unwrap ? "a degenerate cell cannot unwrap a trajectory" : nullptr))) return rc;
     MsdPlanIn in;
     in.F = F; in.n_sel = n_sel; in.n_lags = n_lags; in.direct = direct; in.collective = collective != 0; in.workspace_bytes = workspace_bytes;
     const MsdPlan pl = msd_plan(in, sp_knobs_from_env());
     if (pl.err) { c->msg = std::string("sit_msd: ") + pl.err; return SIT_ERR_INVALID; }
     HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
     const double2 *root = nullptr;
     if (!direct && (rc = sp_roots(c, pl.sp.M, &root))) return rc;
     const i64 B = pl.atoms_per_batch;

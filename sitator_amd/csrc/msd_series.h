@@ -1,10 +1,8 @@
-// The unwrapped series of msd.hip as vanhove.hip shares them: the cell a launch reads and the host function that runs
-// k_msd_shift, the int32 scans and k_msd_series over a batch of atoms.
+// The unwrapped series of msd.hip as vanhove.hip shares them: the host function that runs k_msd_shift, the int32 scans and
+// k_msd_series over a batch of atoms.  The cell a launch reads is that of series.h.
 #pragma once
 #include "series.h"
 #include "msd_plan.h"
-
-struct MsdCell { double cm[9], ci[9]; };
 
 // y [nb][3][F] = x_u[t] - x_u[0] of columns [a0, a0 + nb) of the source, on c->stream.  unwrap: images [3 nb][F] and totals
 // [3 nb][n_chunks] are worked in, the largest residual goes into *status (atomic maximum of the bits); else neither is touched

@@ -3,7 +3,7 @@
 // the sine and cosine, the power step, the term, the origins and their blocks, the order of every sum, the batches, windows
 // and runs a workspace cap allows, the pieces of a call's buffer (sc_layout) - is in scattering_plan.h.
 //
-//   k_sc_frac        f = s - nearbyint(s), s = x . ci (msd_frac, as k_vh_frac) of the columns of the lists, as [frame][3][column]
+//   k_series_frac    (series.h, with ScReduce) f = s - nearbyint(s), s = x . ci of the columns of the lists, as [frame][3][column]
 //   k_sc_density     a run of frames against a tile of q: the three power tables of a tile of (frame, atom) entries are staged
 //                    in LDS, a thread owns a q vector and walks the atoms in selection order; rho [selection][q][F]
 //   k_sc_coherent    one q, one block of origins and a tile of lags: rho_a(t) is read once, the products of every lag are
@@ -18,7 +18,6 @@
 #include <vector>
 
 #include "series.h"
-#include "msd_series.h"
 #include "scattering_plan.h"
 #include "sitator_hip_scattering.h"
 
@@ -31,15 +30,8 @@ struct ScQ {
     i64 q0, nq;                    // the batch: q vectors [q0, q0 + nq)
 };
 
-__global__ __launch_bounds__(SC_THREADS) void k_sc_frac(SeriesSource src, i64 n, i64 f0, i64 nf, MsdCell cell, double *out)
-{
-    const i64 i = (i64)blockIdx.x * SC_THREADS + threadIdx.x;
-    if (i >= nf * n) return;
-    const i64 f = i / n, col = i - f * n;
-    const double *p = src.at(f0 + f, col);
-    const double x = p[0], y = p[1], z = p[2];
-    for (int a = 0; a < 3; a++) out[(f * 3 + a) * n + col] = sc_reduce(msd_frac(cell.ci, a, x, y, z));
-}
+struct ScReduce { __device__ double operator()(double s) const { return sc_reduce(s); } };      // the last step of k_series_frac
+static_assert(SERIES_FRAC_THREADS == SC_THREADS, "SC_MAX_FRAC counts workgroups of SC_THREADS for k_series_frac");
 
 // the table of one axis of one entry of the tile, from the reduced coordinate
 __device__ __forceinline__ void sc_stage(const ScTables &tb, int slot, int a, double f)
@@ -106,7 +98,7 @@ struct ScLags {
 __global__ __launch_bounds__(SC_THREADS) void k_sc_self(SeriesSource src, i64 n_a, MsdCell cell, ScLags g, ScQ qs, ScTables tb)
 {
     const i64 tau = g.lags[blockIdx.z];
-    const i64 n_or = sc_origins(g.F, tau, g.stride), o_lo = (i64)blockIdx.x * SC_BLOCK;
+    const i64 n_or = series_origins(g.F, tau, g.stride), o_lo = (i64)blockIdx.x * SC_BLOCK;
     if (o_lo >= n_or) return;                                     // the whole workgroup: k_sc_reduce reads no such block
     const i64 o_hi = o_lo + SC_BLOCK < n_or ? o_lo + SC_BLOCK : n_or, entries = (o_hi - o_lo) * n_a;
     const i64 j = (i64)blockIdx.y * SC_QTILE + threadIdx.x;
@@ -147,7 +139,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_coherent(const double *rho_a,
     for (int x = half; x < nl; x += SC_THREADS / SC_BLOCK) {
         const i64 tau = g.lags[l0 + x];
         double re = 0.0, im = 0.0;
-        if (o_lo + lane < sc_origins(g.F, tau, g.stride)) {
+        if (o_lo + lane < series_origins(g.F, tau, g.stride)) {
             const double *b = rho_b + (j * g.F + t + tau) * 2;
             sc_cross(ar, ai, b[0], b[1], &re, &im);
         }
@@ -164,7 +156,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_coherent(const double *rho_a,
         }
     }
     __syncthreads();
-    if (threadIdx.x < nl && o_lo < sc_origins(g.F, g.lags[l0 + threadIdx.x], g.stride)) {
+    if (threadIdx.x < nl && o_lo < series_origins(g.F, g.lags[l0 + threadIdx.x], g.stride)) {
         double *o = g.partial + ((((l0 + threadIdx.x) * g.n_blocks + blockIdx.x) * g.qb) + j) * 2;
         o[0] = sc_lds[threadIdx.x * SC_BLOCK * 2];
         o[1] = sc_lds[threadIdx.x * SC_BLOCK * 2 + 1];
@@ -177,7 +169,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_reduce(ScLags g, i64 nq, i64 
     const i64 i = (i64)blockIdx.x * SC_THREADS + threadIdx.x;
     if (i >= g.nl * nq) return;
     const i64 x = i / nq, j = i - x * nq;
-    const i64 nb = sc_blocks(sc_origins(g.F, g.lags[x], g.stride));
+    const i64 nb = sc_blocks(series_origins(g.F, g.lags[x], g.stride));
     double re = 0.0, im = 0.0;
     for (i64 b = 0; b < nb; b++) {
         const double *p = g.partial + ((x * g.n_blocks + b) * g.qb + j) * 2;
@@ -226,37 +218,14 @@ extern "C" int sit_scattering(sit_ctx *c, const double *positions, i64 F, i64 A,
                                    workspace_bytes);
     const ScPlan pl = sc_plan(in, sp_knobs_from_env().workspace);
     if (pl.err) { c->msg = std::string("sit_scattering: ") + pl.err; return SIT_ERR_INVALID; }
-    char text[128];
-    i64 bad = sc_first_outside(lags, n_lags, 0, F - 1);
-    if (bad >= 0) {
-        snprintf(text, sizeof(text), "sit_scattering: lag %lld is outside [0, %lld]", (long long)lags[bad], (long long)(F - 1));
-        c->msg = text;
-        return SIT_ERR_INVALID;
-    }
-    MsdCell cell;
-    for (int i = 0; i < 9; i++) { cell.cm[i] = c->pbc.cm[i]; cell.ci[i] = c->pbc.ci[i]; }
-    {
-        const double *m = cell.cm;
-        const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-        bool ok = std::isfinite(det) && det != 0.0;
-        for (int i = 0; i < 9; i++) ok = ok && std::isfinite(cell.ci[i]);
-        SIT_REQUIRE(c, ok, "sit_scattering: a degenerate cell");
-    }
-    if (!positions) {
-        SIT_REQUIRE(c, c->d_frames && c->A > 0, "sit_scattering: no resident frames (sit_set_frames first)");
-        SIT_REQUIRE(c, F == c->F && A == c->A, "sit_scattering: F or A is not that of the resident frames");
-    }
-    SIT_REQUIRE(c, A >= 1, "sit_scattering: no atom in a frame");
-    for (int which = 0; which < 2; which++) {
-        const i64 *list = which ? atoms_b : atoms_a, n = which ? n_b : n_a;
-        if ((bad = sc_first_outside(list, n, 0, A - 1)) >= 0) {
-            snprintf(text, sizeof(text), "sit_scattering: atom %lld is outside the %lld atoms of a frame", (long long)list[bad], (long long)A);
-            c->msg = text;
-            return SIT_ERR_INVALID;
-        }
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
     int rc;
+    MsdCell cell;
+    if ((rc = series_lags(c, "sit_scattering", lags, n_lags, F)) || (rc = series_cell(c, "sit_scattering", &cell, "a degenerate cell"))) return rc;
+    if (!positions && (rc = series_resident(c, "sit_scattering", F, A))) return rc;
+    SIT_REQUIRE(c, A >= 1, "sit_scattering: no atom in a frame");
+    if ((rc = series_atoms_in_range(c, "sit_scattering", atoms_a, n_a, A)) || (rc = series_atoms_in_range(c, "sit_scattering", atoms_b, n_b, A)))
+        return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
     Scoped work(c), upload(c);
     ScPieces w;
     if ((rc = carve_scratch(c, [&](Carve &cv) { w = sc_layout(cv, pl, in); }, &work))) return rc;
@@ -266,12 +235,8 @@ extern "C" int sit_scattering(sit_ctx *c, const double *positions, i64 F, i64 A,
     HIP_TRY(c, hipMemcpyAsync(w.atoms + n_a, atoms_b, (size_t)n_b * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(w.lags, lags, (size_t)n_lags * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(w.q, q32.data(), (size_t)(3 * n_q) * 4, hipMemcpyHostToDevice, c->stream));
-    SeriesSource src = {c->d_frames, A, w.atoms};
-    if (positions) {
-        HIP_TRY(c, sit_dmalloc(c, &upload.p, (size_t)(F * A) * 24));
-        HIP_TRY(c, hipMemcpyAsync(upload.p, positions, (size_t)(F * A) * 24, hipMemcpyHostToDevice, c->stream));
-        src.pos = (const double *)upload.p;
-    }
+    SeriesSource src;
+    if ((rc = series_frames(c, positions, F, A, w.atoms, upload, &src))) return rc;
     ScTables tb;
     for (int a = 0; a < 3; a++) tb.H[a] = (int)H[a];
     tb.off[0] = 0; tb.off[1] = tb.H[0] + 1; tb.off[2] = tb.H[0] + tb.H[1] + 2;
@@ -294,9 +259,7 @@ extern "C" int sit_scattering(sit_ctx *c, const double *positions, i64 F, i64 A,
         if (coherent_sums) {
             for (i64 f0 = 0; f0 < F; f0 += pl.window) {
                 const i64 nf = F - f0 < pl.window ? F - f0 : pl.window;
-                k_sc_frac<<<dim3((unsigned)((nf * pl.n_cols + SC_THREADS - 1) / SC_THREADS)), dim3(SC_THREADS), 0, c->stream>>>(
-                    src, pl.n_cols, f0, nf, cell, w.frac);
-                HIP_TRY(c, hipGetLastError());
+                if ((rc = series_frac<ScReduce>(c, src, 0, pl.n_cols, f0, nf, cell, w.frac))) return rc;
                 for (i64 sel = 0; sel < pl.n_sel; sel++) {
                     ScDensity d;
                     d.frac = w.frac; d.n_cols = pl.n_cols; d.col0 = sel ? n_a : 0; d.n = sel ? n_b : n_a;
@@ -331,7 +294,7 @@ extern "C" int sit_scattering(sit_ctx *c, const double *positions, i64 F, i64 A,
         for (i64 x = 0; x < n_lags; x++)
             if (lags[x] == 0)                                     // every term is 1: origins x n_a, exactly
                 for (i64 j = 0; j < n_q; j++) {
-                    self_sums[(x * n_q + j) * 2] = (double)(sc_origins(F, 0, origin_stride) * n_a);
+                    self_sums[(x * n_q + j) * 2] = (double)(series_origins(F, 0, origin_stride) * n_a);
                     self_sums[(x * n_q + j) * 2 + 1] = 0.0;
                 }
     return SIT_OK;

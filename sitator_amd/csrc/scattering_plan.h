@@ -1,11 +1,11 @@
 // Every decision of the intermediate scattering function (scattering.hip), in ONE place: the reduction of a fractional
-// coordinate, the hand-written sine and cosine of 2 pi f, the power step and the term of an atom for a q vector, the origins
-// of a lag and their blocks, the order of every sum, the q batch, the frame window and the lags of a launch under a workspace
-// cap, the tile of power tables and its LDS bytes, the validation, and - sc_layout(), the one place that names them - the
-// pieces of a call's device buffer.  Host and device arithmetic only: no HIP call, no context, no side effect
-// (tests/test_scattering_plan.py compiles it with g++ under ASan / UBSan).  No fma and no library sine, cosine or exponential:
-// every product and every sum below is one rounded float64 operation (-ffp-contract=off), which numpy repeats bit for bit
-// (tests/scattering_ref.py).
+// coordinate, the hand-written sine and cosine of 2 pi f, the power step and the term of an atom for a q vector, the blocks
+// of a lag's origins (series_plan.h counts them), the order of every sum, the q batch, the frame window and the lags of a
+// launch under a workspace cap, the tile of power tables and its LDS bytes, the validation, and - sc_layout(), the one place
+// that names them - the pieces of a call's device buffer.  Host and device arithmetic only: no HIP call, no context, no side
+// effect (tests/test_scattering_plan.py compiles it with g++ under ASan / UBSan).  No fma and no library sine, cosine or
+// exponential: every product and every sum below is one rounded float64 operation (-ffp-contract=off), which numpy repeats
+// bit for bit (tests/scattering_ref.py).
 //
 // Definitions.  Cell rows c_0..c_2, ci = inverse(cell^T), q = 2 pi (h ci[0] + k ci[1] + l ci[2]):
 //   phase     s_a = (ci[a][0] x + ci[a][1] y) + ci[a][2] z (msd_frac), f_a = s_a - nearbyint(s_a): NaN where s_a is not finite
@@ -22,7 +22,7 @@
 #include <stdint.h>
 
 #include "scratch_carve.h"
-#include "msd_plan.h"
+#include "series_plan.h"
 
 #define SC_THREADS 256                            // threads of a workgroup of every kernel: four waves
 #define SC_MAX_H 32                               // the largest |h|, |k|, |l|
@@ -37,7 +37,7 @@
 #define SC_LAG_TILE 8                             // lags of a workgroup of k_sc_coherent
 #define SC_RUN 32                                 // frames of a workgroup of k_sc_density
 #define SC_MAX_LAGS_LAUNCH 65535                  // grid.z of k_sc_self
-#define SC_MAX_FRAC ((int64_t)1 << 36)            // (frame, column) elements of one k_sc_frac launch: 2^28 workgroups
+#define SC_MAX_FRAC ((int64_t)1 << 36)            // (frame, column) elements of one k_series_frac launch: 2^28 workgroups
 
 // ---- the phase ----------------------------------------------------------------------------------------------------------
 
@@ -116,10 +116,11 @@ MSD_HD void sc_cross(double ar, double ai, double br, double bi, double *re, dou
     *im = bi * ar - br * ai;
 }
 
-// ---- origins, blocks, the tree --------------------------------------------------------------------------------------------
+// ---- blocks of origins (series_origins of series_plan.h), the tree ----------------------------------------------------------
 
-// origins t = 0, s, 2 s, .. with t + tau <= F - 1 (0 <= tau <= F - 1, s >= 1)
-MSD_HD int64_t sc_origins(int64_t F, int64_t tau, int64_t stride) { return (F - 1 - tau) / stride + 1; }
+// the names the probe of tests/test_scattering_plan.py asks for; the library calls the shared ones
+inline int64_t sc_origins(int64_t F, int64_t tau, int64_t stride) { return series_origins(F, tau, stride); }
+inline int64_t sc_first_outside(const int64_t *list, int64_t n, int64_t lo, int64_t hi) { return series_first_outside(list, n, lo, hi); }
 MSD_HD int64_t sc_blocks(int64_t n_origins) { return (n_origins + SC_BLOCK - 1) / SC_BLOCK; }
 
 // the sum of the SC_BLOCK values of a block in place: steps d = SC_BLOCK / 2, .., 2, 1: v[j] <- v[j] + v[j + d] for j < d; the
@@ -131,7 +132,7 @@ inline double sc_tree(double *v)
     return v[0];
 }
 
-// ---- the validation of the lists --------------------------------------------------------------------------------------
+// ---- the validation of the q list ---------------------------------------------------------------------------------------
 
 // the largest |index| of every axis into H[3]; false for an index beyond SC_MAX_H
 inline bool sc_hmax(const int64_t *q_int, int64_t n_q, int64_t *H)
@@ -144,14 +145,6 @@ inline bool sc_hmax(const int64_t *q_int, int64_t n_q, int64_t *H)
         if (a > H[i % 3]) H[i % 3] = a;
     }
     return true;
-}
-
-// the first element of list outside [lo, hi], or -1
-inline int64_t sc_first_outside(const int64_t *list, int64_t n, int64_t lo, int64_t hi)
-{
-    for (int64_t i = 0; i < n; i++)
-        if (list[i] < lo || list[i] > hi) return i;
-    return -1;
 }
 
 // ---- the plan -----------------------------------------------------------------------------------------------------------
@@ -230,7 +223,7 @@ inline ScPlan sc_plan(const ScPlanIn &in, int64_t default_workspace)
     p.tile = SC_TILE_LDS / (p.row * 16);
     if (p.tile > SC_TILE_MAX) p.tile = SC_TILE_MAX;
     p.lds_bytes = sc_lds_bytes(p.row, p.tile);
-    p.n_blocks = sc_blocks(sc_origins(in.F, 0, in.stride));
+    p.n_blocks = sc_blocks(series_origins(in.F, 0, in.stride));
     // what one q vector, one lag of it and one frame take; the four pieces of the work area start on 256 bytes
     const int64_t q_series = in.want_coherent ? p.n_sel * in.F * 16 : 0, q_lag = p.n_blocks * 16;
     const int64_t frame = in.want_coherent ? 3 * p.n_cols * 8 : 0, slack = 1024;

@@ -3,7 +3,7 @@
 // the split of the pairs over workgroups, the windows and batches a workspace cap allows, the pieces of a call's buffer
 // (vh_layout) - is in vanhove_plan.h; the unwrapped series of the self part are those of msd.hip (msd_series.h).
 //
-//   k_vh_frac        s = x . ci of the atoms of a list, per frame, as [frame][3][atom]
+//   k_series_frac    (series.h, as it is) s = x . ci of the atoms of a list, per frame, as [frame][3][atom]
 //   k_vh_distinct    a workgroup takes one lag, a run of origins and a span of b: each of its four waves takes an item -
 //                    one origin against 64 atoms of b, a lane an atom - stages the atoms of a 64 at a time in LDS and walks
 //                    them (every lane reads the same word: a broadcast); uint32 LDS counters, overflow in a register
@@ -25,16 +25,6 @@ struct VhBins {
     float inv_dr;
     int copies;                    // LDS histograms of a workgroup (vh_lds_bytes)
 };
-
-__global__ __launch_bounds__(256) void k_vh_frac(SeriesSource src, i64 c0, i64 n, i64 f0, i64 nf, MsdCell cell, double *out)
-{
-    const i64 i = (i64)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nf * n) return;
-    const i64 f = i / n, col = i - f * n;
-    const double *p = src.at(f0 + f, c0 + col);
-    const double x = p[0], y = p[1], z = p[2];
-    for (int a = 0; a < 3; a++) out[(f * 3 + a) * n + col] = msd_frac(cell.ci, a, x, y, z);
-}
 
 extern __shared__ double vh_lds[];  // vh_lds_bytes: the edges, the histograms, the tiles of k_vh_distinct
 
@@ -81,7 +71,7 @@ struct VhDistinct {
 __global__ __launch_bounds__(VH_THREADS) void k_vh_distinct(VhDistinct g, VhBins bins, MsdCell cell)
 {
     const i64 tau = g.lags[blockIdx.y];
-    const i64 n_or = vh_origins(g.F, tau, g.stride);
+    const i64 n_or = series_origins(g.F, tau, g.stride);
     i64 o_hi = g.o_end < n_or ? g.o_end : n_or;
     const i64 o_lo = g.o_begin + (i64)blockIdx.x * g.run;
     if (o_lo >= o_hi) return;                                    // the whole workgroup
@@ -140,7 +130,7 @@ __global__ __launch_bounds__(256) void k_vh_positions(SeriesSource src, i64 a0, 
 __global__ __launch_bounds__(VH_THREADS) void k_vh_self(const double *y, i64 F, i64 stride, const i64 *lags, VhBins bins, u64 *counts)
 {
     const i64 tau = lags[blockIdx.y];
-    const i64 n_or = vh_origins(F, tau, stride);
+    const i64 n_or = series_origins(F, tau, stride);
     const i64 o_lo = (i64)blockIdx.x * VH_SELF_RUN;
     if (o_lo >= n_or) return;
     const i64 o_hi = o_lo + VH_SELF_RUN < n_or ? o_lo + VH_SELF_RUN : n_or;
@@ -188,14 +178,6 @@ extern "C" int sit_vanhove_plan(i64 F, i64 n_a, i64 n_b, i64 n_lags, i64 n_bins,
     return p.err ? SIT_ERR_INVALID : SIT_OK;
 }
 
-static int vh_frac(sit_ctx *c, const SeriesSource &src, i64 c0, i64 n, i64 f0, i64 nf, const MsdCell &cell, double *out)
-{
-    if (nf <= 0) return SIT_OK;
-    k_vh_frac<<<dim3((unsigned)((nf * n + 255) / 256)), dim3(256), 0, c->stream>>>(src, c0, n, f0, nf, cell, out);
-    HIP_TRY(c, hipGetLastError());
-    return SIT_OK;
-}
-
 extern "C" int sit_vanhove(sit_ctx *c, const double *positions, i64 F, i64 A, const i64 *atoms_a, i64 n_a, const i64 *atoms_b, i64 n_b,
                            int same, const i64 *lags, i64 n_lags, i64 origin_stride, double r_max, i64 n_bins, int unwrap,
                            i64 workspace_bytes, uint64_t *self_counts, uint64_t *distinct_counts, double *max_residual)
@@ -210,40 +192,14 @@ extern "C" int sit_vanhove(sit_ctx *c, const double *positions, i64 F, i64 A, co
                                    workspace_bytes);
     const VhPlan pl = vh_plan(in, sp_knobs_from_env().workspace);
     if (pl.err) { c->msg = std::string("sit_vanhove: ") + pl.err; return SIT_ERR_INVALID; }
-    for (i64 i = 0; i < n_lags; i++)
-        if (lags[i] < 0 || lags[i] > F - 1) {
-            char text[128];
-            snprintf(text, sizeof(text), "sit_vanhove: lag %lld is outside [0, %lld]", (long long)lags[i], (long long)(F - 1));
-            c->msg = text;
-            return SIT_ERR_INVALID;
-        }
-    MsdCell cell;
-    for (int i = 0; i < 9; i++) { cell.cm[i] = c->pbc.cm[i]; cell.ci[i] = c->pbc.ci[i]; }
-    {
-        const double *m = cell.cm;
-        const double det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
-        bool ok = std::isfinite(det) && det != 0.0;
-        for (int i = 0; i < 9; i++) ok = ok && std::isfinite(cell.ci[i]);
-        SIT_REQUIRE(c, ok, "sit_vanhove: a degenerate cell");
-    }
-    SIT_REQUIRE(c, vh_rmax_ok(r_max, vh_hmin(cell.ci)), "sit_vanhove: r_max is outside (0, hmin / 2 (1 - 2^-30)] of the cell");
-    if (!positions) {
-        SIT_REQUIRE(c, c->d_frames && c->A > 0, "sit_vanhove: no resident frames (sit_set_frames first)");
-        SIT_REQUIRE(c, F == c->F && A == c->A, "sit_vanhove: F or A is not that of the resident frames");
-    }
-    SIT_REQUIRE(c, A >= 1, "sit_vanhove: no atom in a frame");
-    for (int which = 0; which < 2; which++) {
-        const i64 *list = which ? atoms_b : atoms_a, n = which ? n_b : n_a;
-        for (i64 i = 0; i < n; i++)
-            if (list[i] < 0 || list[i] >= A) {
-                char text[128];
-                snprintf(text, sizeof(text), "sit_vanhove: atom %lld is outside the %lld atoms of a frame", (long long)list[i], (long long)A);
-                c->msg = text;
-                return SIT_ERR_INVALID;
-            }
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
     int rc;
+    MsdCell cell;
+    if ((rc = series_lags(c, "sit_vanhove", lags, n_lags, F)) || (rc = series_cell(c, "sit_vanhove", &cell, "a degenerate cell"))) return rc;
+    SIT_REQUIRE(c, vh_rmax_ok(r_max, vh_hmin(cell.ci)), "sit_vanhove: r_max is outside (0, hmin / 2 (1 - 2^-30)] of the cell");
+    if (!positions && (rc = series_resident(c, "sit_vanhove", F, A))) return rc;
+    SIT_REQUIRE(c, A >= 1, "sit_vanhove: no atom in a frame");
+    if ((rc = series_atoms_in_range(c, "sit_vanhove", atoms_a, n_a, A)) || (rc = series_atoms_in_range(c, "sit_vanhove", atoms_b, n_b, A))) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
     Scoped work(c), upload(c);
     VhPieces w;
     if ((rc = carve_scratch(c, [&](Carve &cv) { w = vh_layout(cv, pl, in); }, &work))) return rc;
@@ -257,16 +213,12 @@ extern "C" int sit_vanhove(sit_ctx *c, const double *positions, i64 F, i64 A, co
     HIP_TRY(c, hipMemcpyAsync(w.atoms + n_a, atoms_b, (size_t)n_b * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(w.lags, lags, (size_t)n_lags * 8, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(w.e2, e2.data(), (size_t)nb1 * 8, hipMemcpyHostToDevice, c->stream));
-    SeriesSource src = {c->d_frames, A, w.atoms};
-    if (positions) {
-        HIP_TRY(c, sit_dmalloc(c, &upload.p, (size_t)(F * A) * 24));
-        HIP_TRY(c, hipMemcpyAsync(upload.p, positions, (size_t)(F * A) * 24, hipMemcpyHostToDevice, c->stream));
-        src.pos = (const double *)upload.p;
-    }
+    SeriesSource src;
+    if ((rc = series_frames(c, positions, F, A, w.atoms, upload, &src))) return rc;
     VhBins bins;
     bins.e2 = w.e2; bins.n_bins = n_bins; bins.inv_dr = (float)((double)n_bins / r_max); bins.copies = in.hist_copies;
     const size_t lds = (size_t)pl.lds_bytes;
-    const i64 most_origins = vh_origins(F, 0, origin_stride);
+    const i64 most_origins = series_origins(F, 0, origin_stride);
     if (distinct_counts) {
         HIP_TRY(c, lds_limit((const void *)k_vh_distinct, lds, c->device));
         VhDistinct g;
@@ -280,18 +232,18 @@ extern "C" int sit_vanhove(sit_ctx *c, const double *positions, i64 F, i64 A, co
             return SIT_OK;
         };
         if (pl.window >= F) {                                    // every frame held: all lags at once
-            if ((rc = vh_frac(c, src, 0, n_a, 0, F, cell, w.sa)) || (rc = vh_frac(c, src, n_a, n_b, 0, F, cell, w.sb))) return rc;
+            if ((rc = series_frac(c, src, 0, n_a, 0, F, cell, w.sa)) || (rc = series_frac(c, src, n_a, n_b, 0, F, cell, w.sb))) return rc;
             g.fa0 = g.fb0 = 0; g.o_begin = 0; g.o_end = most_origins;
             for (i64 l0 = 0; l0 < n_lags; l0 += VH_MAX_GRID_YZ)
                 if ((rc = launch(l0, n_lags - l0 < VH_MAX_GRID_YZ ? n_lags - l0 : VH_MAX_GRID_YZ))) return rc;
         } else {
             // a lag at a time: the frames of a window of origins for a, the same frames a lag later for b
             for (i64 l = 0; l < n_lags; l++) {
-                const i64 tau = lags[l], n_or = vh_origins(F, tau, origin_stride);
+                const i64 tau = lags[l], n_or = series_origins(F, tau, origin_stride);
                 for (i64 o0 = 0; o0 < n_or; o0 += pl.origins_per_window) {
                     const i64 o1 = o0 + pl.origins_per_window < n_or ? o0 + pl.origins_per_window : n_or;
                     const i64 f0 = o0 * origin_stride, nf = (o1 - 1) * origin_stride - f0 + 1;
-                    if ((rc = vh_frac(c, src, 0, n_a, f0, nf, cell, w.sa)) || (rc = vh_frac(c, src, n_a, n_b, f0 + tau, nf, cell, w.sb))) return rc;
+                    if ((rc = series_frac(c, src, 0, n_a, f0, nf, cell, w.sa)) || (rc = series_frac(c, src, n_a, n_b, f0 + tau, nf, cell, w.sb))) return rc;
                     g.fa0 = f0; g.fb0 = f0 + tau; g.o_begin = o0; g.o_end = o1;
                     if ((rc = launch(l, 1))) return rc;
                 }

@@ -1,8 +1,9 @@
 // Every decision of the van Hove correlation function (vanhove.hip), in ONE place: the bin of a squared distance, the table
-// of squared edges, the fractional coordinate and the minimum image of a pair, the origins of a lag, the largest r_max a
-// cell allows, the split of the pairs over workgroups, the windows of frames and the batches of atoms that fit a workspace
-// cap, and - vh_layout(), the one place that names them - the pieces of a call's device buffer.  Host and device arithmetic
-// only: no HIP call, no context, no side effect (tests/test_vanhove_plan.py compiles it with g++ under ASan / UBSan).
+// of squared edges, the fractional coordinate and the minimum image of a pair (the origins of a lag are series_plan.h's),
+// the largest r_max a cell allows, the split of the pairs over workgroups, the windows of frames and the batches of atoms
+// that fit a workspace cap, and - vh_layout(), the one place that names them - the pieces of a call's device buffer.  Host
+// and device arithmetic only: no HIP call, no context, no side effect (tests/test_vanhove_plan.py compiles it with g++ under
+// ASan / UBSan).
 //
 // Definitions.  Cell rows c_0..c_2, ci = inverse(cell^T), lists a and b of atoms, lags tau, origins
 // t = 0, s, 2 s, .. while t + tau <= F - 1:
@@ -16,7 +17,7 @@
 #include <stdint.h>
 
 #include "scratch_carve.h"
-#include "msd_plan.h"
+#include "series_plan.h"
 
 #define VH_THREADS 256                            // threads of a workgroup of either kernel: four waves
 #define VH_WAVE 64
@@ -27,7 +28,7 @@
 #define VH_TARGET_PAIRS ((int64_t)1 << 20)        // pairs a distinct workgroup aims at: a flush of n_bins + 1 atomics per 2^20
 #define VH_MAX_PAIRS ((int64_t)1 << 31)           // pairs a workgroup may count: its LDS counters are uint32
 #define VH_SELF_RUN 4096                          // origins of a self workgroup: sixteen per thread
-#define VH_MAX_FRAC ((int64_t)1 << 36)            // (frame, atom) elements of one k_vh_frac launch: 2^28 workgroups
+#define VH_MAX_FRAC ((int64_t)1 << 36)            // (frame, atom) elements of one k_series_frac launch: 2^28 workgroups
 #define VH_MAX_GRID_YZ 65535
 
 // ---- the bins ---------------------------------------------------------------------------------------------------------
@@ -69,10 +70,10 @@ MSD_HD double vh_image_r2(double ds0, double ds1, double ds2, const double *cm)
 
 MSD_HD double vh_r2(double dx, double dy, double dz) { return (dx * dx + dy * dy) + dz * dz; }
 
-// ---- lags, origins, r_max ---------------------------------------------------------------------------------------------
+// ---- r_max (the origins of a lag: series_origins of series_plan.h) --------------------------------------------------------
 
-// origins t = 0, s, 2 s, .. with t + tau <= F - 1 (0 <= tau <= F - 1, s >= 1)
-MSD_HD int64_t vh_origins(int64_t F, int64_t tau, int64_t stride) { return (F - 1 - tau) / stride + 1; }
+// the name the probe of tests/test_vanhove_plan.py asks for; the library calls series_origins
+inline int64_t vh_origins(int64_t F, int64_t tau, int64_t stride) { return series_origins(F, tau, stride); }
 
 // the smallest perpendicular height of the cell: 1 / |row a of ci| (what the context keeps as hmin once it has a basis)
 inline double vh_hmin(const double *ci)
