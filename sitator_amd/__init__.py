@@ -20,6 +20,7 @@ from .dynamics import VanHoveCorrelation, VanHoveResult, RadialDistribution, RDF
 from .dynamics import IntermediateScattering, ScatteringResult, StructureFactor, StructureFactorResult, q_vectors  # noqa: F401
 from .density import DensityResult, IonicDensity, gaussian_stencil  # noqa: F401
 from .percolation import ComponentsResult, PercolationResult, density_components, density_percolation  # noqa: F401
+from .landscape import EnergyLandscape, LandscapeResult  # noqa: F401
 from .merging import MergeSites, MergeSitesError, MergedSitesTooDistantError  # noqa: F401
 from .recenter import RecenterTrajectory  # noqa: F401
 from .misc import GenerateAroundSites, NAvgsPerSite  # noqa: F401
