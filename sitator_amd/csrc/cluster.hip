@@ -510,16 +510,17 @@ static void predict_form(const sit_ctx *c, PredPlan &p)
     p.wide_lds = lds && p.wide_lds_bytes <= 150 * 1024;
 }
 
-int wide_list_carve(sit_ctx *c, int nseg, i64 seg_cap, unsigned **wcount, i32 **wlist)
+int wide_list_carve(sit_ctx *c, int nseg, i64 seg_cap, unsigned **wcount, i32 **wlist, bool persistent)
 {
-    const int rc = ensure_scratch(c, ((i64)nseg * seg_cap + 2 * nseg + 64) * 4);
+    const int rc = ensure_scratch(c, ((i64)nseg * seg_cap + 2 * nseg + 64) * 4, persistent);
     if (rc) return rc;
     *wcount = (unsigned *)c->d_scratch;
     *wlist = (i32 *)c->d_scratch + ((2 * nseg + 63) / 64 * 64);
     return SIT_OK;
 }
 
-static int predict_plan(sit_ctx *c, PredPlan &p)
+// persistent: the segment lengths of this very layout were zeroed by predict_reset_with_fill, ahead of the fill kernel
+static int predict_plan(sit_ctx *c, PredPlan &p, bool persistent = false)
 {
     predict_form(c, p);
     // the listing kernel: persistent workgroups, each with its own segment of the wide-row list; in LDS two workgroups
@@ -529,7 +530,7 @@ static int predict_plan(sit_ctx *c, PredPlan &p)
     const i64 blocks = (c->N + p.nt - 1) / p.nt;
     p.nseg = (int)std::min<i64>(blocks, (i64)cu_count(c) * p.per_cu);
     p.seg_cap = (blocks + p.nseg - 1) / p.nseg * p.nt;             // rows a workgroup can meet
-    return wide_list_carve(c, p.nseg, p.seg_cap, &p.wcount, &p.wlist);
+    return wide_list_carve(c, p.nseg, p.seg_cap, &p.wcount, &p.wlist, persistent);
 }
 
 // sit_fill with assign = 1: the words of the fill and of the assignment behind it in ONE launch, ahead of the fill
@@ -585,7 +586,11 @@ static int run_predict(sit_ctx *c, double threshold, bool words_reset = false)
     bool counted = false;
     if (c->max_col <= PRED_MAXCOL) {
         PredPlan pp;
-        if ((rc = predict_plan(c, pp))) return rc;
+        // PERSISTENT scratch where words_reset: sit_fill (assign = 1, not fused) had predict_reset_with_fill lay out the same
+        // list and zero its segment lengths before the fill kernel; nothing carves the scratch between there and here but the
+        // profiling stops of k_fill3 (SITATOR_DEBUG_STOP >= 10, fill3.hip: their span buffer lies over these words and is
+        // zeroed - rows and labels of such a run are incomplete anyway)
+        if ((rc = predict_plan(c, pp, words_reset))) return rc;
         if (getenv("SITATOR_DEBUG_SHAPE")) fprintf(stderr, "predict: lds %zu nt %d per_cu %d nseg %d seg_cap %lld narrow_lds %d wide_lds %d rows_W %lld\n", pp.lds, pp.nt, pp.per_cu, pp.nseg, (long long)pp.seg_cap, (int)pp.narrow_lds, (int)pp.wide_lds, (long long)c->rows_W);
         // sit_fill with assign = 1 has reset these words together with its own, ahead of the fill kernel
         if (!words_reset && (rc = reset_predict_words(c, pp.narrow_lds, pp.wcount, 2 * pp.nseg))) return rc;
@@ -813,9 +818,9 @@ static int fit_ensure(sit_ctx *c, i64 cap)
     if (c->fit_cap >= cap && c->d_fit_centers) return SIT_OK;
     double *ncen = nullptr, *nnrm = nullptr;
     i64 *ncnt = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&ncen, (size_t)(cap * c->D) * 8));
-    HIP_TRY(c, hipMalloc((void **)&nnrm, (size_t)cap * 8));
-    HIP_TRY(c, hipMalloc((void **)&ncnt, (size_t)cap * 8));
+    HIP_TRY(c, sit_raw_malloc((void **)&ncen, (size_t)(cap * c->D) * 8));
+    HIP_TRY(c, sit_raw_malloc((void **)&nnrm, (size_t)cap * 8));
+    HIP_TRY(c, sit_raw_malloc((void **)&ncnt, (size_t)cap * 8));
     if (c->fit_K > 0 && c->d_fit_centers && c->fit_cap > 0) {
         HIP_TRY(c, hipMemcpyAsync(ncen, c->d_fit_centers, (size_t)(c->fit_K * c->D) * 8, hipMemcpyDeviceToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(nnrm, c->d_fit_nrm2, (size_t)c->fit_K * 8, hipMemcpyDeviceToDevice, c->stream));

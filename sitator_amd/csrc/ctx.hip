@@ -57,7 +57,34 @@ void pool_trim(size_t cap)
 }
 }  // namespace
 
+hipError_t sit_debug_fill(void *p, size_t bytes)
+{
+    const int v = debug_fill_byte();
+    if (v < 0 || !p || bytes == 0) return hipSuccess;
+    // whatever still works on these bytes ends first (the scratch of a context is filled between two of its calls), and
+    // the fill has landed before any stream - the non-blocking copy streams too - touches them
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemset(p, v, bytes);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    return e;
+}
+
+hipError_t sit_raw_malloc(void **p, size_t bytes)
+{
+    const hipError_t e = hipMalloc(p, bytes);
+    return e == hipSuccess ? sit_debug_fill(*p, bytes) : e;
+}
+
+static hipError_t dmalloc_unfilled(sit_ctx *c, void **p, size_t bytes);
+
 hipError_t sit_dmalloc(sit_ctx *c, void **p, size_t bytes)
+{
+    if (bytes == 0) bytes = 8;
+    const hipError_t e = dmalloc_unfilled(c, p, bytes);
+    return e == hipSuccess ? sit_debug_fill(*p, bytes) : e;
+}
+
+static hipError_t dmalloc_unfilled(sit_ctx *c, void **p, size_t bytes)
 {
     *p = nullptr;
     if (bytes == 0) bytes = 8;
@@ -225,9 +252,9 @@ extern "C" int sit_create(const double *cell, const double *cell_inv, int device
     for (int i = 0; i < T_N; i++) { HIP_TRY(c, hipEventCreate(&c->tev0[i])); HIP_TRY(c, hipEventCreate(&c->tev1[i])); }
     HIP_TRY(c, hipHostMalloc(&c->h_pinned, 1024));      // [0, 512): one-off read-backs; [512, 1024): the results of deferred fills
     // the error key and the counters sit side by side: one read-back per call
-    HIP_TRY(c, hipMalloc((void **)&c->d_err, sizeof(u64) * 17));
+    HIP_TRY(c, sit_raw_malloc((void **)&c->d_err, sizeof(u64) * 17));
     c->d_scal = c->d_err + 1;
-    HIP_TRY(c, hipMalloc((void **)&c->d_fit_K, sizeof(i64)));
+    HIP_TRY(c, sit_raw_malloc((void **)&c->d_fit_K, sizeof(i64)));
     return SIT_OK;
 }
 

@@ -1859,7 +1859,7 @@ int fitfast_stream(sit_ctx *c, const i32 *nnz, const i32 *idx, const double *val
     { const char *wp = getenv("SITATOR_WALK_PAIR"); if (wp) walk_pair = wp[0] != '0' && weights == nullptr; }
     if (walk_pair) HIP_TRY(c, lds_limit((const void *)k_fs_walk_pair, walk_pair_lds, c->device));
     const char *tp = getenv("SITATOR_FF_TRACE");              // diagnostics: one line per step
-    if (tp && !f->d_trace) { HIP_TRY(c, hipMalloc((void **)&f->d_trace, (size_t)FS_TRACE_CAP * 48)); HIP_TRY(c, hipMemset(f->d_trace, 0, (size_t)FS_TRACE_CAP * 48)); }
+    if (tp && !f->d_trace) { HIP_TRY(c, sit_raw_malloc((void **)&f->d_trace, (size_t)FS_TRACE_CAP * 48)); HIP_TRY(c, hipMemset(f->d_trace, 0, (size_t)FS_TRACE_CAP * 48)); }
     i64 base = 0;                                             // rows consumed before the current control chain
     int B = f->B_keep;                                        // (a pipelined run streams its rows in 4-16 calls: 8 doubling steps each)
     for (;;) {
@@ -1879,7 +1879,7 @@ int fitfast_stream(sit_ctx *c, const i32 *nnz, const i32 *idx, const double *val
             FSArgs a;
             memset(&a, 0, sizeof(a));
             a.s = s; a.r = rb; a.threshold = threshold;
-            if (!f->d_args) HIP_TRY(c, hipMalloc((void **)&f->d_args, sizeof(FSArgs)));
+            if (!f->d_args) HIP_TRY(c, sit_raw_malloc((void **)&f->d_args, sizeof(FSArgs)));
             if (!f->args_set || memcmp(&f->h_args, &a, sizeof(FSArgs)) != 0) {
                 f->h_args = a; f->args_set = true;
                 HIP_TRY(c, hipMemcpyAsync(f->d_args, &f->h_args, sizeof(FSArgs), hipMemcpyHostToDevice, c->stream));

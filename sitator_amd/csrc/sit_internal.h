@@ -10,6 +10,7 @@
 
 #include "sitator_hip.h"
 #include "scratch_carve.h"
+#include "debug_fill.h"
 
 typedef int64_t i64;
 typedef int32_t i32;
@@ -203,12 +204,20 @@ static inline hipError_t lds_limit(const void *kernel, size_t bytes, int device)
     return e;
 }
 
-// Device memory of a context (ctx.hip).  Buffers of SITATOR_POOL_MIN_MB (64) and more are not returned to the driver
-// when a context lets go of them but kept, up to SITATOR_POOL_GB (64) in all, for the next context of the process:
-// on this driver a multi-GB hipFree followed by a hipMalloc of the same pages stalls for about a second per 27 GB.
-// Contents are whatever the last user left: every caller initialises what it reads.
+// Device memory of a context (ctx.hip).  Buffers of SITATOR_POOL_MIN_MB (1) and more are not returned to the driver
+// when a context lets go of them but kept, up to SITATOR_POOL_GB (by default: as much as the contexts of the process have
+// held at once) in all, for the next context of the process: on this driver a multi-GB hipFree followed by a hipMalloc of
+// the same pages stalls for about a second per 27 GB.
+// Contents are whatever the last user left: every caller initialises what it reads.  SITATOR_DEBUG_FILL (debug_fill.h)
+// makes that checkable: with it every buffer handed out here, every use of the context's scratch and every raw allocation
+// (sit_raw_malloc) starts out as that byte.
 hipError_t sit_dmalloc(sit_ctx *c, void **p, size_t bytes);
 void sit_dfree(sit_ctx *c, void *p);
+// SITATOR_DEBUG_FILL: `bytes` at p set to the byte, done on return on every stream (the device is idle before and after);
+// nothing at all when the knob is off
+hipError_t sit_debug_fill(void *p, size_t bytes);
+// hipMalloc for the few small buffers that go round the pool (freed with sit_dfree or hipFree), under the debug fill
+hipError_t sit_raw_malloc(void **p, size_t bytes);
 
 template <typename T>
 static inline int dev_alloc(sit_ctx *c, T **p, i64 n)
@@ -229,12 +238,19 @@ static inline int dev_upload(sit_ctx *c, T **p, const T *h, i64 n)
     return SIT_OK;
 }
 
-static inline int ensure_scratch(sit_ctx *c, i64 bytes)
+// The first `bytes` of the context's scratch buffer, for the caller to write before it reads (SITATOR_DEBUG_FILL: they
+// start out as the fill on EVERY call, not only when the buffer grows).  persistent: the caller comes back for a piece an
+// earlier call of this function laid out and wrote - it is not filled, and the call site says who wrote it; a buffer that
+// would have to grow cannot hold that piece, and the call fails.
+static inline int ensure_scratch(sit_ctx *c, i64 bytes, bool persistent = false)
 {
-    if (bytes <= c->scratch_bytes) return SIT_OK;
-    if (c->d_scratch) { (void)hipFree(c->d_scratch); c->d_scratch = nullptr; c->scratch_bytes = 0; }
-    HIP_TRY(c, hipMalloc(&c->d_scratch, (size_t)bytes));
-    c->scratch_bytes = bytes;
+    SIT_REQUIRE(c, !persistent || bytes <= c->scratch_bytes, "scratch: a persistent piece is larger than the buffer it was written to (internal error)");
+    if (bytes > c->scratch_bytes) {
+        if (c->d_scratch) { (void)hipFree(c->d_scratch); c->d_scratch = nullptr; c->scratch_bytes = 0; }
+        HIP_TRY(c, hipMalloc(&c->d_scratch, (size_t)bytes));
+        c->scratch_bytes = bytes;
+    }
+    if (!persistent && bytes > 0) HIP_TRY(c, sit_debug_fill(c->d_scratch, (size_t)bytes));
     return SIT_OK;
 }
 
@@ -561,8 +577,8 @@ bool fill3_eligible(sit_ctx *c);
 // not, the rows were stored whatever `store` says and the caller runs the assignment kernels)
 int fill3_launch(sit_ctx *c, const sit_fill_params *p, bool store, i64 f_lo = 0, i64 f_hi = -1, bool fuse = false, bool *fused = nullptr);
 // cluster.hip: the wide-row list in the scratch buffer - two length words per segment, then from the next 64-word
-// boundary nseg segments of seg_cap rows
-int wide_list_carve(sit_ctx *c, int nseg, i64 seg_cap, unsigned **wcount, i32 **wlist);
+// boundary nseg segments of seg_cap rows (persistent: see ensure_scratch)
+int wide_list_carve(sit_ctx *c, int nseg, i64 seg_cap, unsigned **wcount, i32 **wlist, bool persistent = false);
 // cluster.hip: the rows k_fill3 listed (segments of the scratch buffer), then the label counts
 int predict_listed_rows(sit_ctx *c, double threshold, i32 *wlist, unsigned *wcount, i64 seg_cap, int nseg);
 // transfer.hip: copies between pageable host memory and the device, the large ones through the pinned staging ring

@@ -945,7 +945,7 @@ def test_mcl_reductions_are_exact_and_reproducible(oracle):
 
 @pytest.mark.gpu
 def test_large_buffers_are_recycled_between_contexts_with_identical_results():
-    """Device buffers of 64 MB and more go to the library's pool when a context closes and to the next context that
+    """Device buffers of 1 MB and more go to the library's pool when a context closes and to the next context that
     asks (ctx.hip): the second context must not see what the first left in them."""
     from sitator_amd import synth, _lib
     host = synth.config_host("C2")
